@@ -7,18 +7,26 @@ reference's own per-stage semantics (warpPerspective + overwrite paste, Stitcher
 and --blend feather the linear feather blend.  One "step" = one stitch launch over --frames rig
 captures already resident in HBM (4 camera frames each), producing --frames mosaics: the
 streaming gather kernel over every tile, then (blend modes) the blend kernel over the tiles the
-blend changes.  Captures 0, F/2 and F-1 of the last timed step are checked against the CPU
-restatement on every rank ("max_abs_diff", max over ranks and captures).
+blend changes.
+
+A plain run (python bench.py --gpus 1 --steps N --warmup W) does only what the headline figure
+needs: it sets up the rig and the plan, warms up, times exactly N steps, writes the outputs of the
+last one with --dump-outputs DIR (dump_outputs), and prints the result line ("value", and
+"ms_per_step": the milliseconds one timed step took).  Everything below is measured or checked
+only with --full.
+
+--full: captures 0, F/2 and F-1 of the last timed step are checked against the CPU restatement on
+every rank ("max_abs_diff", max over ranks and captures).
 
 Multi-GPU (python bench.py --gpus N, or python -m torch.distributed.run ... bench.py --gpus N):
 one process per GPU; capture g goes to rank g mod N (weak scaling, no data-path collective);
-barrier + synchronize around the timed region, time = max over ranks.  Every N (1 included) also
-measures, in the same rank processes, BASELINE configs[3] (C4: 8-camera cylinder + graph-cut +
-multi-band, the mosaics gathered to rank 0 through mcs_group_gather) and configs[4] (C5: each
-rank streams its share of 4 x 3840x2160 host captures through its own mcs_stream pipeline; the
-last mosaics gathered to rank 0), under "also".
+barrier + synchronize around the timed region, time = max over ranks.  With --full every N (1
+included) also measures, in the same rank processes, BASELINE configs[3] (C4: 8-camera cylinder +
+graph-cut + multi-band, the mosaics gathered to rank 0 through mcs_group_gather) and configs[4]
+(C5: each rank streams its share of 4 x 3840x2160 host captures through its own mcs_stream
+pipeline; the last mosaics gathered to rank 0), under "also".
 
-Extra fields: "roofline" (HBM-bound; algorithmic bytes = SURVEY.md 8d's B_frame -- every camera
+Extra fields of --full: "roofline" (HBM-bound; algorithmic bytes = SURVEY.md 8d's B_frame -- every camera
 frame read once + the mosaic written once -- per launch, over the launch's average duration
 measured with HIP events on its stream; "touched" prices only the source pixels the mosaic reads;
 both are lower bounds for the blend modes, whose seam tiles re-read their neighbourhoods),
@@ -70,7 +78,8 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--gather", choices=["after", "timed", "none"], default="after",
                     help="N > 1: deliver every rank's F mosaics to rank 0 (RCCL point-to-point "
-                         "over xGMI) after the timed region ('after': a verified one-shot gather "
+                         "over xGMI) after the timed region ('after', with --full: a verified "
+                         "one-shot gather "
                          "plus a second timed loop of stitch + gather steps, reported as "
                          "'gather'), or as part of every timed step of the line itself ('timed')")
     ap.add_argument("--stream-frames", type=int, default=120,
@@ -87,6 +96,14 @@ def parse(argv=None):
     ap.add_argument("--pmc-json", default=None,
                     help="counter summary for roofline.traffic (default profiles/pmc_latest.json, "
                          "profiles/pmc_latest_cyl.json with --rig cylinder)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline line: parity of captures 0, F/2, F-1 against the CPU "
+                         "restatement, the paste-only reference launch, roofline, the CPU "
+                         "baseline, the gather lines at N > 1 and the companion lines under "
+                         "'also' (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left in the output "
+                         "batch as DIR/<name>.npy (dump_outputs)")
     return ap.parse_args(argv)
 
 
@@ -163,6 +180,36 @@ def pipeline_loop(submit, collect, depth, frames, warmup, units_per_capture, ctx
     return timed_rate(step, frames, warmup, drain, units_per_capture, ctx)
 
 
+DUMP_SAMPLE = 4 << 20   # elements of mosaics_sample (16 MB as float32)
+
+
+def dump_outputs(dirname, mosaics, ctx):
+    """--dump-outputs: what the last timed step left in this rank's output batch (`mosaics`: its
+    F mosaics, a (F, rows, bytes per row) uint8 tensor), as .npy files by which two builds can be
+    compared output for output (the inputs are seeded: the same arguments give the same frames).
+    mosaics_sample (float32): the whole batch while it has at most DUMP_SAMPLE elements, else
+    DUMP_SAMPLE elements at fixed seeded positions of the flattened batch.  mosaic_row_sums
+    (float64, (F, rows)): the exact sum of the bytes of every mosaic row, so every output byte
+    counts.  At N > 1 every rank writes <name>_rank<r>.npy.  Returns the file names."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    F, H, W = mosaics.shape
+    if F * H * W <= DUMP_SAMPLE:
+        sample = mosaics.to(torch.float32)
+    else:
+        at = torch.from_numpy(np.random.default_rng(0).integers(0, F * H * W, DUMP_SAMPLE))
+        at = at.to(mosaics.device)
+        sample = mosaics[at // (H * W), at % (H * W) // W, at % W].to(torch.float32)
+    arrays = {"mosaics_sample": sample,
+              "mosaic_row_sums": mosaics.sum(dim=2, dtype=torch.int64).to(torch.float64)}
+    suffix = "" if ctx.world == 1 else f"_rank{ctx.rank}"
+    names = []
+    for name, a in arrays.items():
+        names.append(name + suffix + ".npy")
+        np.save(os.path.join(dirname, names[-1]), a.cpu().numpy())
+    return names
+
+
 # ---- the GPU lines -------------------------------------------------------------------------------
 
 def main():
@@ -186,8 +233,8 @@ def main():
         torch.cuda.set_device(0)
     ctx = Ctx(world, rank, torch.device("cuda", torch.cuda.current_device()))
 
-    result = rig_line(args, ctx, cpu=world == 1 and not args.no_cpu_baseline)
-    if not args.no_also and args.rig == "chain" and args.blend == "multiband":
+    result = rig_line(args, ctx, cpu=args.full and world == 1 and not args.no_cpu_baseline)
+    if args.full and not args.no_also and args.rig == "chain" and args.blend == "multiband":
         # BASELINE configs[3] and configs[4] at this N, in these same rank processes
         also = {"c4_cylinder_multiband": guarded(lambda: rig_line(c4_args(args), ctx, cpu=False),
                                                  ctx, "c4"),
@@ -275,13 +322,15 @@ def c4_args(args):
     a = copy.copy(args)
     a.rig, a.cams, a.blend, a.seam = "cylinder", None, "multiband", "graphcut"
     a.pmc_json = None
+    a.dump_outputs = None
     return a
 
 
 def rig_line(args, ctx, cpu):
-    """One bench line over a rig plan (args.rig): the timed launches, the paste-only reference,
-    roofline, parity of captures 0, F/2, F-1 on every rank, the gather to rank 0 at N > 1, and the
-    CPU baseline (cpu=True, rank 0).  Returns the line on rank 0, None elsewhere."""
+    """One bench line over a rig plan (args.rig): set-up, the timed launches and --dump-outputs;
+    with --full also the paste-only reference, roofline, parity of captures 0, F/2, F-1 on every
+    rank, the gather to rank 0 at N > 1, and the CPU baseline (cpu=True, rank 0).  Returns the
+    line on rank 0, None elsewhere."""
     import torch
     from multicamera_stitching_amd import rig, shard, _capi
     from multicamera_stitching_amd.StitcherClass import _stage_desc
@@ -356,7 +405,7 @@ def rig_line(args, ctx, cpu):
 
     step = stitch
     group = recv = None
-    if world > 1 and args.gather != "none":
+    if world > 1 and (args.gather == "timed" or (args.gather == "after" and args.full)):
         group = shard.mcs_group(dev.index)
         recv = (torch.empty((world,) + tuple(d_out.shape), dtype=torch.uint8, device=dev)
                 if rank == 0 else None)
@@ -393,22 +442,28 @@ def rig_line(args, ctx, cpu):
     launch_ms = shard.max_over_ranks([float(np.mean([a.elapsed_time(b) for a, b in ev]))],
                                      device=dev)[0]
     value = timed["value"]
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, d_out[:, :, :out_w * C], ctx)
     # the captures parity checks, read back before anything else reuses d_out
-    checked = check_captures(F)
+    checked = check_captures(F) if args.full else []
     got = {f: d_out[f, :, :out_w * C].reshape(out_h, out_w, C).cpu().numpy() for f in checked}
     gather = None
     if group is not None:
-        try:
-            gather = gather_all(d_out, args, stitch, group, recv, stream, ctx, mpix_per_launch)
-        except Exception as e:   # (outside the timed region: the line still reports the run)
-            gather = {"error": f"{type(e).__name__}: {e}"}
+        if args.full:
+            try:
+                gather = gather_all(d_out, args, stitch, group, recv, stream, ctx,
+                                    mpix_per_launch)
+            except Exception as e:   # (outside the timed region: the line still reports the run)
+                gather = {"error": f"{type(e).__name__}: {e}"}
         group.close()
         del recv
 
     # the same launch with the reference's paste (cylinder: the hard seam) and no blend pass:
     # the blend's share of the time
     paste_ms = None
-    if blend not in (_capi.MCS_BLEND_NONE, _capi.MCS_BLEND_SEAM) and not args.no_paste_ref:
+    if (args.full and blend not in (_capi.MCS_BLEND_NONE, _capi.MCS_BLEND_SEAM)
+            and not args.no_paste_ref):
         ref = make_plan()
         if cyl:
             if seam_k is not None:
@@ -434,10 +489,60 @@ def rig_line(args, ctx, cpu):
         paste_ms = shard.max_over_ranks([float(np.mean([a.elapsed_time(b) for a, b in evr]))],
                                         device=dev)[0]
         ref.close()
-    fp = plan.footprint()
+    fp = plan.footprint() if args.full else None
     del d_cams, d_out
     plan.close()
     torch.cuda.empty_cache()
+
+    result = {
+        "metric": ("stitched MPix/sec (8-cam 360 cylindrical rig)" if cyl else
+                   "stitched MPix/sec (4-cam 1080p rig)"),
+        "value": round(value, 3),
+        "unit": "MPix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(timed["ms_per_step"], 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic",
+        "config": {
+            "workload": describe_workload(args, cyl, n_cams),
+            "blend": args.blend,
+            "mosaic": [out_h, out_w, C],
+            "frames_per_step": F,
+            "super_mode": bool(args.super_mode),
+            "parallelism": (f"captures sharded over {world} GPU(s) (capture g -> rank g mod "
+                            f"{world}), no data-path collective" +
+                            ("; every step gathers all mosaics to rank 0"
+                             if world > 1 and args.gather == "timed" else "")),
+        },
+        "plan": {"prepare_ms_once": round(prep_ms, 3), "tiles": plan_stats["tiles"],
+                 "lds_tiles": plan_stats["lds_tiles"],
+                 "direct_tiles": plan_stats["direct_tiles"],
+                 "blend_tiles_32x64": plan_stats["blend_tiles"],
+                 "mb_bands": plan_stats["mb_bands"],
+                 "mb_bands_lds_ring": plan_stats["mb_bands_lds"],
+                 "big_footprint_tiles": plan_stats["big_tiles"],
+                 "mb_mixed_px_per_capture": plan_stats["mb_mixed_px"],
+                 "mb_r1_entries_per_capture": plan_stats["mb_r1_entries"],
+                 "table_mb": round(plan_stats["table_bytes"] / 1e6, 2),
+                 # streaming reads per launch: what the footprint DMAs fetch (row spans in 16-B
+                 # chunks) and the footprint boxes they are cut from
+                 "stream_dma_gb_per_launch": round(F * plan_stats["dma_bytes_per_capture"] / 1e9, 4),
+                 "stream_box_gb_per_launch": round(F * plan_stats["box_bytes_per_capture"] / 1e9, 4),
+                 "seams": None if seam_k is None else {
+                     "method": "graph-cut (mcs_plan_find_seams, device push-relabel)",
+                     "grid_log2": seam_k, "ms_once": round(seam_ms, 2)}},
+        # (the HIP events around the timed launches themselves)
+        "kernels": {"launch_ms": round(launch_ms, 4)},
+    }
+    if dumped is not None:
+        result["outputs"] = dumped
+    if not args.full:
+        return result if rank == 0 else None
 
     # algorithmic bytes per launch: B_frame = every camera frame read once + the
     # mosaic written once (the roofline's bytes); beside it the touched-pixel figure: only the
@@ -492,56 +597,16 @@ def rig_line(args, ctx, cpu):
     if rank != 0:
         return None
     cpu_line = cpu_baseline(runner, cams, args, out_w, out_h, host) if cpu else None
-    result = {
-        "metric": ("stitched MPix/sec (8-cam 360 cylindrical rig)" if cyl else
-                   "stitched MPix/sec (4-cam 1080p rig)"),
-        "value": round(value, 3),
-        "unit": "MPix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(timed["ms_per_step"], 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic",
-        "config": {
-            "workload": describe_workload(args, cyl, n_cams),
-            "blend": args.blend,
-            "mosaic": [out_h, out_w, C],
-            "frames_per_step": F,
-            "super_mode": bool(args.super_mode),
-            "parallelism": (f"captures sharded over {world} GPU(s) (capture g -> rank g mod "
-                            f"{world}), no data-path collective" +
-                            ("; every step gathers all mosaics to rank 0"
-                             if world > 1 and args.gather == "timed" else "")),
-        },
+    # (the touched source beside the plan's streaming reads)
+    result["plan"]["touched_source_gb_per_launch"] = round(F * sum(fp) * C / 1e9, 4)
+    if seam_k is not None:
+        result["plan"]["seams"]["labels_equal_restatement"] = seams_equal
+    result["kernels"]["paste_only_launch_ms"] = None if paste_ms is None else round(paste_ms, 4)
+    result.update({
         "max_abs_diff": max_abs,
         "checked_captures": {"per_rank": checked, "ranks": world,
                              "max_abs_diff_rank0": {str(f): d for f, d in diffs.items()}},
         "gather": gather,
-        "plan": {"prepare_ms_once": round(prep_ms, 3), "tiles": plan_stats["tiles"],
-                 "lds_tiles": plan_stats["lds_tiles"],
-                 "direct_tiles": plan_stats["direct_tiles"],
-                 "blend_tiles_32x64": plan_stats["blend_tiles"],
-                 "mb_bands": plan_stats["mb_bands"],
-                 "mb_bands_lds_ring": plan_stats["mb_bands_lds"],
-                 "big_footprint_tiles": plan_stats["big_tiles"],
-                 "mb_mixed_px_per_capture": plan_stats["mb_mixed_px"],
-                 "mb_r1_entries_per_capture": plan_stats["mb_r1_entries"],
-                 "table_mb": round(plan_stats["table_bytes"] / 1e6, 2),
-                 # streaming reads per launch: what the footprint DMAs fetch (row spans in 16-B
-                 # chunks) and the footprint boxes they are cut from, beside the touched source
-                 "stream_dma_gb_per_launch": round(F * plan_stats["dma_bytes_per_capture"] / 1e9, 4),
-                 "stream_box_gb_per_launch": round(F * plan_stats["box_bytes_per_capture"] / 1e9, 4),
-                 "touched_source_gb_per_launch": round(F * sum(fp) * C / 1e9, 4),
-                 "seams": None if seam_k is None else {
-                     "method": "graph-cut (mcs_plan_find_seams, device push-relabel)",
-                     "grid_log2": seam_k, "ms_once": round(seam_ms, 2),
-                     "labels_equal_restatement": seams_equal}},
-        "kernels": {"launch_ms": round(launch_ms, 4),
-                    "paste_only_launch_ms": None if paste_ms is None else round(paste_ms, 4)},
         "roofline": {
             "bound": "hbm",
             "kernel": "mcs_stream_c%d%s (one launch)" % (
@@ -583,7 +648,7 @@ def rig_line(args, ctx, cpu):
                 "ms_per_launch": round(paste_ms, 4)},
         },
         "cpu_baseline": cpu_line,
-    }
+    })
     return result
 
 
@@ -832,7 +897,7 @@ def stub_main(args, world, rank):
         dist.init_process_group("gloo")
     ctx = Ctx(world, rank, torch.device("cpu"))
 
-    def stub_rig_line(F, out_h, out_w, C, metric, with_gather, line_name="c2"):
+    def stub_rig_line(F, out_h, out_w, C, metric, with_gather, line_name="c2", dump=None):
         # capture g of the job = a known byte pattern rolled by g; rank r holds g = f * N + r
         base = torch.arange(out_h * out_w * C, dtype=torch.int64).remainder(251).to(torch.uint8)
         d_out = torch.empty((F, out_h * out_w * C), dtype=torch.uint8)
@@ -844,6 +909,15 @@ def stub_main(args, world, rank):
         mpix = F * out_w * out_h / 1e6
         tr = timed_rate(stitch, args.steps, args.warmup, lambda: None, mpix, ctx)
         _inject_failure(ctx, line_name)
+        line = {"metric": metric, "value": round(tr["value"], 6), "unit": "MPix/s",
+                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(tr["ms_per_step"], 4), "rank0_seconds": tr["seconds_rank"],
+                "max_seconds": tr["seconds_max"], "mpix_per_step_per_rank": mpix,
+                "higher_is_better": True, "scaling": "weak", "config": {"workload": "stub"}}
+        if dump:
+            line["outputs"] = dump_outputs(dump, d_out.view(F, out_h, out_w * C), ctx)
+        if not args.full:
+            return line if rank == 0 else None
         # every rank checks captures 0, F/2, F-1 against an independent restatement (numpy)
         diffs = []
         for f in check_captures(F):
@@ -865,13 +939,10 @@ def stub_main(args, world, rank):
                                            "ms_per_step": round(tg["ms_per_step"], 4)}
         if rank != 0:
             return None
-        return {"metric": metric, "value": round(tr["value"], 6), "unit": "MPix/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                "ms_per_step": round(tr["ms_per_step"], 4), "rank0_seconds": tr["seconds_rank"],
-                "max_seconds": tr["seconds_max"], "mpix_per_step_per_rank": mpix,
-                "higher_is_better": True, "scaling": "weak", "max_abs_diff": max_abs,
-                "checked_captures": {"per_rank": check_captures(F), "ranks": world},
-                "gather": gather, "config": {"workload": "stub"}}
+        line.update({"max_abs_diff": max_abs,
+                     "checked_captures": {"per_rank": check_captures(F), "ranks": world},
+                     "gather": gather})
+        return line
 
     def stub_stream_line(frames=12, depth=3):
         src = [np.full((8, 12, 3), (rank * 7 + k) % 251, np.uint8) for k in range(2)]
@@ -907,9 +978,9 @@ def stub_main(args, world, rank):
                 "max_abs_diff": max_abs, "gather": gather, "host": workers}
 
     result = stub_rig_line(4, 32, 48, 3, "stub (orchestration rehearsal, no GPU)",
-                           with_gather=True)
+                           with_gather=True, dump=args.dump_outputs)
     also = None
-    if not args.no_also:
+    if args.full and not args.no_also:
         also = {"c4_cylinder_multiband": guarded(
                     lambda: stub_rig_line(4, 16, 96, 3, "stub C4", True, "c4"), ctx, "c4"),
                 "c5_stream_4k": guarded(stub_stream_line, ctx, "c5")}

@@ -26,7 +26,7 @@ def _line(out):
 
 
 def test_bench_gpus2_spawns_two_ranks():
-    r = _run(["--gpus", "2", "--stub", "--steps", "4", "--warmup", "1"])
+    r = _run(["--gpus", "2", "--stub", "--full", "--steps", "4", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     res = _line(r.stdout)
     assert res["n_gpus"] == 2
@@ -55,7 +55,7 @@ def test_bench_gpus2_spawns_two_ranks():
 
 
 def test_bench_gpus1_stub_single_process():
-    r = _run(["--stub", "--steps", "2", "--warmup", "0"])
+    r = _run(["--stub", "--full", "--steps", "2", "--warmup", "0"])
     assert r.returncode == 0, r.stderr[-2000:]
     res = _line(r.stdout)
     assert res["n_gpus"] == 1 and res["gather"] is None
@@ -74,7 +74,7 @@ def test_bench_gpus4_rank_failure_reported_not_hung():
     gather collectives): the other ranks stop at their next collective point instead of waiting
     out the 300 s collective timeout, rank 0's JSON line carries rank 1's message in that line,
     and the headline line and the other companion line stand (bench.py guarded)."""
-    r = _run(["--gpus", "4", "--stub", "--steps", "2", "--warmup", "1"],
+    r = _run(["--gpus", "4", "--stub", "--full", "--steps", "2", "--warmup", "1"],
              env={"MCS_BENCH_INJECT_FAIL": "1:c4"})
     assert r.returncode == 0, r.stderr[-2000:]
     res = _line(r.stdout)
@@ -90,7 +90,7 @@ def test_bench_gpus4_copy_pool_shared_by_ranks():
     """The C5 line's host copy pool is sized per rank: the node's CPU quota divided among the
     LOCAL_WORLD_SIZE ranks (mcs_stream_copy_workers), so N ranks never start more copy threads
     than the node's CPUs (verdict round 5: 7 per rank x 8 ranks on a 16-CPU quota)."""
-    r = _run(["--gpus", "4", "--stub", "--steps", "2", "--warmup", "1"])
+    r = _run(["--gpus", "4", "--stub", "--full", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     host = _line(r.stdout)["also"]["c5_stream_4k"]["host"]
     assert host["local_world_size"] == 4
@@ -98,3 +98,56 @@ def test_bench_gpus4_copy_pool_shared_by_ranks():
     for w in host["copy_workers_per_rank"]:
         assert 0 <= w <= max(0, min(7, (usable // 4) // 2 - 1)), host
     assert sum(w + 1 for w in host["copy_workers_per_rank"]) <= max(usable, 4), host
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full a run times exactly --steps steps and prints the headline fields only (no
+    parity, gather or companion lines); --dump-outputs writes the output batch of the last timed
+    step -- here small enough to be written whole -- and a second run writes the same arrays."""
+    import numpy as np
+    args = ["--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--dump-outputs"]
+    runs = [_run(args + [str(tmp_path / d)]) for d in ("a", "b")]
+    for r in runs:
+        assert r.returncode == 0, r.stderr[-2000:]
+    res = _line(runs[0].stdout)
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["n_gpus"] == 1
+    assert abs(res["ms_per_step"] - res["max_seconds"] / 3 * 1e3) <= 1e-4
+    assert abs(res["value"] - res["mpix_per_step_per_rank"] * 3 / res["max_seconds"]) <= \
+        1e-5 * res["value"] + 1e-6
+    for moved in ("also", "max_abs_diff", "checked_captures", "gather"):
+        assert moved not in res, moved
+    assert sorted(res["outputs"]) == ["mosaic_row_sums.npy", "mosaics_sample.npy"]
+    sample = np.load(tmp_path / "a" / "mosaics_sample.npy")
+    rows = np.load(tmp_path / "a" / "mosaic_row_sums.npy")
+    assert sample.dtype == np.float32 and sample.shape == (4, 32, 48 * 3)
+    assert rows.dtype == np.float64 and rows.shape == (4, 32)
+    base = (np.arange(32 * 48 * 3) % 251).astype(np.float32)
+    for f in range(4):      # the stub's capture f: the byte pattern rolled by f + 1
+        assert np.array_equal(sample[f].ravel(), np.roll(base, f + 1))
+    assert np.array_equal(rows, sample.astype(np.float64).sum(axis=2))
+    for name in res["outputs"]:
+        assert np.array_equal(np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name))
+
+
+def test_dump_outputs_samples_a_large_batch_at_seeded_positions(tmp_path):
+    """A batch above bench.DUMP_SAMPLE elements is written as DUMP_SAMPLE of them, at positions
+    that depend on the batch's shape alone (a strided view as the GPU line passes it: the row
+    padding is never read); the row sums still cover every byte."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    g = torch.Generator().manual_seed(1)
+    padded = torch.randint(0, 256, (3, 1200, 1280), dtype=torch.uint8, generator=g)
+    batch = padded[:, :, :1203]
+    assert batch.numel() > bench.DUMP_SAMPLE
+    names = bench.dump_outputs(str(tmp_path), batch, bench.Ctx(1, 0, torch.device("cpu")))
+    assert sorted(names) == ["mosaic_row_sums.npy", "mosaics_sample.npy"]
+    sample = np.load(tmp_path / "mosaics_sample.npy")
+    assert sample.dtype == np.float32 and sample.shape == (bench.DUMP_SAMPLE,)
+    flat = batch.contiguous().numpy().ravel()
+    at = np.random.default_rng(0).integers(0, flat.size, bench.DUMP_SAMPLE)
+    assert np.array_equal(sample, flat[at].astype(np.float32))
+    rows = np.load(tmp_path / "mosaic_row_sums.npy")
+    assert rows.dtype == np.float64
+    assert np.array_equal(rows, batch.numpy().astype(np.float64).sum(axis=2))

@@ -2,6 +2,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
-mkdir -p gpurun_out
 R="$GRAFT_REPO_ROOT"
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof" -o run -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline "$@" > "$R/gpurun_out/prof.log" 2>&1
+O="${MCS_PROF_DIR:-$R/bench_out}"
+mkdir -p "$O"
+cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o run -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline "$@" > "$O/prof.log" 2>&1

@@ -11,8 +11,8 @@ count (calibration stitches, plan preparation, warm-up and the parity check are 
 Per window: every mcs_* kernel's dispatch count, mean / median / min / max duration (us); per
 launch the span from its first dispatch's start to its last dispatch's end (the same quantity
 the bench's HIP events bracket, minus event overhead).  With --bench-line (the JSON line of the
-same run) the roofline fractions are recomputed from those spans and the line's algorithmic
-bytes (SURVEY.md 8d B_frame and the touched-pixel figure).  --trim writes the raw trace rows
+same run, a bench.py --full one) the roofline fractions are recomputed from those spans and the
+line's algorithmic bytes (SURVEY.md 8d B_frame and the touched-pixel figure).  --trim writes the raw trace rows
 (every column) of the dispatches inside the marker windows, markers included: the committed
 record of the timed launches.
 """
