@@ -108,7 +108,8 @@ int mcs_plan_create(const mcs_stage_desc *stages, int n_stages, int cam0_w, int 
 /* A camera of a rotation-only rig projected onto a cylinder (SURVEY.md section 8 NS-6 / C4:
  * 8 cameras at 45 degree yaw steps around one centre, f = 1100).  R: rig -> camera rotation,
  * row-major (a rig ray d maps to R d in camera coordinates, z forward, y down); f, cx, cy:
- * pinhole intrinsics in pixels; w, h: frame size.  Undistorted frames (see mcs_undistort_*). */
+ * pinhole intrinsics in pixels; w, h: frame size.  The frames are undistorted ones
+ * (mcs_undistort_*), or raw ones for a camera given its lens with mcs_plan_set_lens. */
 typedef struct mcs_cyl_camera {
     double R[9];
     double f, cx, cy;
@@ -142,6 +143,29 @@ int mcs_plan_create_undistort(const double *K, const double *dist, int n_dist, i
  * value per axis, (short)(i >> 5) * 32 + (i & 31) with i = cvRound(32 u). */
 int mcs_undistort_map_host(const double *K, const double *dist, int n_dist, int w, int h,
                            int32_t *map);
+/* Lens of camera `cam` (sorted-label order): the plan then samples RAW frames of that camera,
+ * with no undistortion pass before it.  Every stage map of the camera ends in its lens: the
+ * position in the camera's undistorted image (a double: the homography's or the cylinder's
+ * projection, or camera 0's integer placement) goes through cv::initUndistortRectifyMap's model
+ * with R = I and newCameraMatrix = K, per position, and only then is rounded to the sampling
+ * fixed point; edge distances, ownership, seams and all blend modes are measured in the raw
+ * frame.  Positions beyond the radius where the radial polynomial folds back (see
+ * mcs_lens_map_host) are outside the camera.
+ * K: 3x3 row-major with zero skew and last row 0 0 1; dist / n_dist as
+ * mcs_plan_create_undistort (0, 4, 5, 8, 12 or 14 coefficients, tilt terms 0; anything else:
+ * MCS_E_UNSUPPORTED).  K == NULL removes the lens.  A lens is never dropped because its
+ * coefficients are zero: the identity lens runs the lens arithmetic and returns its input bit
+ * for bit.  Chain, cylindrical and warp plans; undistort (table) plans: MCS_E_UNSUPPORTED.  Bad
+ * camera index or non-finite values: MCS_E_INVALID.  Drops the prepared tables, as
+ * mcs_plan_set_blend does.  Host-side only. */
+int mcs_plan_set_lens(mcs_plan *plan, int cam, const double *K, const double *dist, int n_dist);
+/* The lens map alone on the host (no device): n positions uv (u, v pairs) of the undistorted
+ * image -> xy (raw x, y pairs); r2 > r2max gives NaN, NaN.  *r2max (optional) receives the valid
+ * radius squared of the normalised position ((u - cx) / fx, (v - cy) / fy): the first
+ * r = i / 256, i = 1..2048, at which the radial denominator is not positive or r * num / den
+ * stops growing, one step back; +inf when there is none. */
+int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const double *uv, int n,
+                      double *xy, double *r2max);
 int mcs_plan_destroy(mcs_plan *plan);
 int mcs_plan_out_shape(const mcs_plan *plan, int *w, int *h, int *channels);
 int mcs_plan_describe(const mcs_plan *plan, mcs_flat_desc *out);
@@ -164,7 +188,8 @@ int mcs_plan_prepare(mcs_plan *plan, void *stream);
  * LDS-path tiles' footprint DMAs read (each row's span in 16-byte chunks) and the bytes of their
  * footprint boxes (every row at the box width); stats[16..19] = the multi-band sweep's strips
  * (MCS_MB_SWEEP=1 plans; 0 otherwise), the mosaic pixels they write per capture, threads per
- * sweep workgroup, and the rows of its precomputed sample descriptors.  Entries past 19 read 0. */
+ * sweep workgroup, and the rows of its precomputed sample descriptors; stats[20] = cameras with
+ * a lens (mcs_plan_set_lens).  Entries past 20 read 0. */
 int mcs_plan_stats(const mcs_plan *plan, int64_t *stats, int n);
 
 /* Blend mode of the plan (MCS_BLEND_*; default NONE = the reference's paste).  Changing it drops
@@ -236,8 +261,8 @@ int mcs_stitch_device(mcs_plan *plan, const uint8_t *const *d_cams,
  * usable the moment mcs_plan_create returns (host flattening only, microseconds) -- the path for
  * geometry that changes every capture (per-frame homographies, SURVEY.md 8 C3: estimate ->
  * stitch).  Paste (MCS_BLEND_NONE) and MCS_BLEND_SEAM plans; the same pixels as
- * mcs_stitch_device.  Replaces, per capture, StitcherBase.calibrate (:258-354) followed by
- * StitcherBase.stitch (:211-256). */
+ * mcs_stitch_device, lensed plans (mcs_plan_set_lens) included.  Replaces, per capture,
+ * StitcherBase.calibrate (:258-354) followed by StitcherBase.stitch (:211-256). */
 int mcs_stitch_direct(mcs_plan *plan, const uint8_t *const *d_cams,
                       const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
                       int64_t out_frame_stride, int n_frames, void *stream);

@@ -128,7 +128,7 @@ def _plan_key(descs, cam0_shape, channels, interp, device):
 class _Transient(object):
     """Mixin: keeps GPU state (plans, locks) out of pickles and deep copies."""
 
-    _TRANSIENT = ("_mcs_cache",)
+    _TRANSIENT = ("_mcs_cache", "_mcs_lenses")
 
     def __getstate__(self):
         st = dict(self.__dict__)
@@ -273,6 +273,33 @@ class Stitcher(_Transient, Debugger):
         cam0 = self.stitchers[0].BimgSize if self.stitchers else None
         return _get_plan(self, self.stitchers, cam0, channels, interp, device)
 
+    def set_lenses(self, lenses):
+        """Cameras that deliver RAW frames (extension): {label: (K, dist) or None}.
+
+        K is the 3x3 camera matrix at the camera's calibrated size and dist its OpenCV distortion
+        vector, as the caller would pass them to cv2.undistort before ``stitch``.  With a lens
+        set, ``stitch`` takes that camera's frames as the sensor delivers them: the undistortion
+        is part of the plan's own map (mcs_plan_set_lens), one resampling instead of two and no
+        undistorted copy.  None (or a missing label) removes a camera's lens; ``set_lenses({})``
+        removes all.  Not pickled: a loaded stitcher has no lenses until they are set again.
+        """
+        labels = [str(l) for l in self.img_labels]
+        table = {}
+        for label, lens in dict(lenses or {}).items():
+            if str(label) not in labels:
+                raise KeyError("no camera labelled {!r}".format(label))
+            if lens is None:
+                continue
+            K, dist = lens
+            k = np.array(K, dtype=np.float64).reshape(3, 3)
+            d = np.array([] if dist is None else dist, dtype=np.float64).reshape(-1)
+            table[labels.index(str(label))] = (k, d)
+        if table:
+            self.__dict__["_mcs_lenses"] = table
+        else:
+            self.__dict__.pop("_mcs_lenses", None)
+        return self
+
 
 # =============================================================================================
 class StitcherBase(_Transient, Debugger):
@@ -393,12 +420,18 @@ def _get_plan(owner, chain, cam0_shape, channels, interp=None, device=None):
     blend = _env_blend()
     descs = [_stage_desc(sb) for sb in chain]
     key = _plan_key(descs, cam0_shape, channels, interp, device) + (blend,)
+    # Stitcher.set_lenses: camera index (sorted-label order) -> (K, dist)
+    lenses = owner.__dict__.get("_mcs_lenses") or {}
+    if lenses:
+        key += (tuple((i, k.tobytes(), d.tobytes()) for i, (k, d) in sorted(lenses.items())),)
     cache = owner._cache()
 
     def make():
         plan = _capi.Plan(descs, cam0_shape[1], cam0_shape[0], channels, interp, device)
         if blend != _capi.MCS_BLEND_NONE:
             plan.set_blend(blend)
+        for i, (k, d) in sorted(lenses.items()):
+            plan.set_lens(i, k, d)
         return plan
     return cache.get(key, make)
 

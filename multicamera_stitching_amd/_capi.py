@@ -51,6 +51,7 @@ EXPORTS = (
     "mcs_rig_job_submit", "mcs_rig_job_wait", "mcs_rig_job_counts", "mcs_rig_job_destroy",
     "mcs_seam_graphcut_device", "mcs_plan_seam_stats", "mcs_chain_stages",
     "mcs_rig_job_wait_stitch", "mcs_rig_job_create_batch", "mcs_rig_job_wait_stitch_batch",
+    "mcs_plan_set_lens", "mcs_lens_map_host",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -253,6 +254,10 @@ def load() -> ctypes.CDLL:
         L.mcs_plan_create_undistort.restype = I
         L.mcs_undistort_map_host.argtypes = [P, P, I, I, I, P]
         L.mcs_undistort_map_host.restype = I
+        L.mcs_plan_set_lens.argtypes = [P, I, P, P, I]
+        L.mcs_plan_set_lens.restype = I
+        L.mcs_lens_map_host.argtypes = [P, P, I, P, I, P, P]
+        L.mcs_lens_map_host.restype = I
         L.mcs_match_l2_knn2.argtypes = [P, I, P, I, I, P, P, P, I, P]
         L.mcs_match_l2_knn2.restype = I
         L.mcs_match_l2_knn2_host.argtypes = [P, I, P, I, I, P, P, P, I]
@@ -506,8 +511,8 @@ class Plan:
         check(self._lib.mcs_plan_prepare(self._h, ctypes.c_void_p(int(stream))))
 
     def stats(self) -> dict:
-        arr = (ctypes.c_int64 * 20)()
-        check(self._lib.mcs_plan_stats(self._h, arr, 20))
+        arr = (ctypes.c_int64 * 21)()
+        check(self._lib.mcs_plan_stats(self._h, arr, 21))
         return {"prepared": bool(arr[0]), "tiles": arr[1], "lds_tiles": arr[2],
                 "direct_tiles": arr[3], "table_bytes": arr[4], "blend": arr[5],
                 "blend_tiles": arr[6], "mb_owners": arr[7], "mb_degraded_tiles": arr[8],
@@ -515,12 +520,25 @@ class Plan:
                 "mb_mixed_px": arr[12], "mb_r1_entries": arr[13],
                 "dma_bytes_per_capture": arr[14], "box_bytes_per_capture": arr[15],
                 "mb_sweep_strips": arr[16], "mb_sweep_px": arr[17],
-                "mb_sweep_threads": arr[18], "mb_sweep_desc_rows": arr[19]}
+                "mb_sweep_threads": arr[18], "mb_sweep_desc_rows": arr[19],
+                "lens_cams": arr[20]}
 
     def set_blend(self, mode: int):
         """MCS_BLEND_NONE (reference paste), MCS_BLEND_FEATHER, MCS_BLEND_MULTIBAND or
         MCS_BLEND_SEAM (owner only)."""
         check(self._lib.mcs_plan_set_blend(self._h, int(mode)))
+        return self
+
+    def set_lens(self, cam: int, K, dist=None):
+        """mcs_plan_set_lens: camera `cam` (sorted-label order) delivers RAW frames, undistorted
+        inside the plan's own map by the lens (K, dist); K=None removes the lens."""
+        if K is None:
+            check(self._lib.mcs_plan_set_lens(self._h, int(cam), None, None, 0))
+            return self
+        k, d = _lens_args(K, dist)
+        check(self._lib.mcs_plan_set_lens(self._h, int(cam), k.ctypes.data_as(ctypes.c_void_p),
+                                          d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
+                                          int(d.size)))
         return self
 
     def footprint(self):
@@ -970,6 +988,29 @@ def undistort_map_host(K, dist, w: int, h: int) -> np.ndarray:
                                    int(d.size), int(w), int(h),
                                    out.ctypes.data_as(ctypes.c_void_p)))
     return out
+
+
+def _lens_args(K, dist):
+    k = np.ascontiguousarray(np.asarray(K, np.float64).reshape(9))
+    d = np.ascontiguousarray(np.asarray(dist if dist is not None else [], np.float64).reshape(-1))
+    return k, d
+
+
+def lens_map_host(K, dist, uv, with_r2max: bool = False):
+    """mcs_lens_map_host: positions uv (..., 2) of the undistorted image -> positions in the raw
+    frame (same shape, float64; NaN beyond the valid radius), optionally with r2max."""
+    L = load()
+    k, d = _lens_args(K, dist)
+    pts = np.ascontiguousarray(np.asarray(uv, np.float64))
+    if pts.shape[-1:] != (2,):
+        raise ValueError("uv must have shape (..., 2)")
+    out = np.empty_like(pts)
+    r2 = ctypes.c_double(0.0)
+    check(L.mcs_lens_map_host(k.ctypes.data_as(ctypes.c_void_p),
+                              d.ctypes.data_as(ctypes.c_void_p) if d.size else None, int(d.size),
+                              pts.ctypes.data_as(ctypes.c_void_p), int(pts.size // 2),
+                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(r2)))
+    return (out, r2.value) if with_r2max else out
 
 
 def match_l2_knn2(query, train, device: int = 0):

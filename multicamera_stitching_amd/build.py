@@ -33,7 +33,7 @@ HOST_SRC = ["mcs_plan.cpp", "hip_rt.cpp", "mcs_runtime.cpp", "mcs_capi.cpp", "mc
             "mcs_stream.cpp", "mcs_seam.cpp", "mcs_refine.cpp", "mcs_group.cpp", "mcs_rig.cpp",
             "mcs_chain.cpp"]
 HEADERS = ["mcs_kparams.h", "mcs_dev.h", "mcs_fparams.h", "mcs_common.h", "hip_rt.h", "mcs_blend.h", "mcs_ransac_core.h",
-           "mcs_orb_core.h", "mcs_orb_pattern.h", "mcs_feat_int.h"]
+           "mcs_orb_core.h", "mcs_orb_pattern.h", "mcs_feat_int.h", "mcs_lens_core.h"]
 INC = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
 DEVICE_FLAGS = [
@@ -41,6 +41,11 @@ DEVICE_FLAGS = [
     "-O3", "-std=c++17",
     # bit-exact OpenCV arithmetic: no FMA contraction of the FP64 coordinate map
     "-ffp-contract=off", "-fno-fast-math", "-Wall",
+    # KParams is a by-value kernel argument: clang copies it to a private alloca and InstCombine
+    # turns the copy back into kernarg loads only while the alloca has at most this many users
+    # (default 300).  mcs_prepare_* is past that since the lens code: without the higher limit it
+    # keeps the 2.6 KB copy in scratch, per lane.
+    "-mllvm", "-instcombine-max-copied-from-constant-users=4096",
 ]
 HOST_FLAGS = [
     "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unused-parameter",

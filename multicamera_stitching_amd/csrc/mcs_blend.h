@@ -16,25 +16,29 @@
 
 namespace mcs {
 
-// Camera slot s of the plan: 0 = camera 0 (integer offset), j+1 = stage j's camera.
+// Camera slot s of the plan: 0 = camera 0 (integer offset, or its lens), j+1 = stage j's camera.
 template <int INTERP>
 __device__ __forceinline__ void slot_xy(const KParams &P, int s, int x, int y, int &x32, int &y32,
                                         int &cam, int &w, int &h)
 {
+    int X, Y;
     if (s == 0) {
         cam = 0;
         w = P.cam0_w;
         h = P.cam0_h;
-        x32 = (x + P.cam0_offx) * 32;
-        y32 = (y + P.cam0_offy) * 32;
-        return;
+        if (!cam0_lensed(P)) {
+            x32 = (x + P.cam0_offx) * 32;
+            y32 = (y + P.cam0_offy) * 32;
+            return;
+        }
+        cam0_lens_map<INTERP>(P, x, y, X, Y);
+    } else {
+        const KStage &S = P.st[s - 1];
+        cam = S.cam;
+        w = S.src_w;
+        h = S.src_h;
+        stage_map<INTERP>(P, S, x, y, X, Y);
     }
-    const KStage &S = P.st[s - 1];
-    cam = S.cam;
-    w = S.src_w;
-    h = S.src_h;
-    int X, Y;
-    stage_map<INTERP>(P, S, x, y, X, Y);
     if (INTERP == MCS_INTER_NEAREST) {
         x32 = sat_i16(X) * 32;
         y32 = sat_i16(Y) * 32;

@@ -102,6 +102,11 @@ struct mcs_plan {
     bool single = false;
     std::vector<int32_t> map_tab;
     int32_t *d_map = nullptr;
+    // lenses (mcs_plan_set_lens): host rows of the cameras in kp.lens_mask, the device table
+    // (MCS_MAX_CAMS rows, allocated once) and whether it lags the host rows
+    mcs::Lens lens[MCS_MAX_CAMS] = {};
+    double *d_lens = nullptr;
+    bool lens_stale = false;
 };
 
 int mcs::plan_device(const mcs_plan *plan) { return plan ? plan->device : 0; }
@@ -1083,9 +1088,17 @@ void release_tables(const Api *A, mcs_plan *p)
     p->n_fallback = p->n_blend = 0;
 }
 
-// Cylindrical plans: the per-column / per-row table on the plan's device (once).
+// Cylindrical plans: the per-column / per-row table on the plan's device (once); table plans:
+// their map; lensed plans: the lens rows (again after every mcs_plan_set_lens).
 int ensure_cyl(const Api *A, mcs_plan *p, hipStream_t s)
 {
+    if (p->kp.lens_mask && (!p->d_lens || p->lens_stale)) {
+        if (!p->d_lens) HIP_TRY(A->hipMalloc((void **)&p->d_lens, sizeof(p->lens)));
+        HIP_TRY(A->hipMemcpyAsync(p->d_lens, p->lens, sizeof(p->lens), hipMemcpyHostToDevice, s));
+        HIP_TRY(A->hipStreamSynchronize(s));
+        p->lens_stale = false;
+        p->kp.lens_tab = p->d_lens;
+    }
     if (!p->map_tab.empty() && !p->d_map) {
         const size_t bytes = p->map_tab.size() * sizeof(int32_t);
         HIP_TRY(A->hipMalloc((void **)&p->d_map, bytes));
@@ -1499,6 +1512,7 @@ int launch_stitch(const Api *A, mcs_plan *p, const mcs::KParams &kp, int n_frame
     mcs::KParams P = kp;
     P.cyl_tab = p->kp.cyl_tab;   // set by prepare on a cylindrical plan's first use
     P.map_tab = p->kp.map_tab;   // (table plans)
+    P.lens_tab = p->kp.lens_tab; // (lensed plans)
     P.skip = p->kp.skip;         // (multi-band sweep plans: set by prepare)
     if (uniform) return launch_pair(A, p, k, P, n_frames, s);
     for (int f = 0; f < n_frames; f++) {
@@ -1734,7 +1748,8 @@ int mcs_undistort_map_host(const double *K, const double *dist, int n_dist, int 
 int mcs_plan_destroy(mcs_plan *p)
 {
     if (!p) return MCS_OK;
-    bool touched = p->stream || p->d_out || p->d_tiles || p->side || p->side2;
+    bool touched = p->stream || p->d_out || p->d_tiles || p->side || p->side2 || p->d_lens ||
+                   p->d_cyl || p->d_map || p->d_seam;
     for (int i = 0; i < MCS_MAX_CAMS; i++) touched = touched || p->d_cams[i];
     if (touched) {
         const Api *A = mcs::rt::api();
@@ -1752,6 +1767,7 @@ int mcs_plan_destroy(mcs_plan *p)
             if (p->d_cyl) (void)A->hipFree(p->d_cyl);
             if (p->d_seam) (void)A->hipFree(p->d_seam);
             if (p->d_map) (void)A->hipFree(p->d_map);
+            if (p->d_lens) (void)A->hipFree(p->d_lens);
             if (p->side) (void)A->hipStreamSynchronize(p->side);
             if (p->side2) (void)A->hipStreamSynchronize(p->side2);
             if (p->stream) (void)A->hipStreamDestroy(p->stream);
@@ -1951,6 +1967,7 @@ int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *
     if (rc) return rc;
     kp.cyl_tab = p->kp.cyl_tab;
     kp.map_tab = p->kp.map_tab;
+    kp.lens_tab = p->kp.lens_tab;
     kp.seam_hint = p->kp.seam_hint;
     const int gx = (p->fd.out_w + mcs::kTileW - 1) / mcs::kTileW;
     const int gy = (p->fd.out_h + mcs::kTileH - 1) / mcs::kTileH;
@@ -2022,6 +2039,58 @@ int mcs_plan_set_blend(mcs_plan *p, int mode)
     }
     p->blend = mode;
     p->kp.blend = mode;
+    return MCS_OK;
+}
+
+int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist, int n_dist)
+{
+    mcs::clear_error();
+    if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
+    if (!p->map_tab.empty())
+        return mcs::fail(MCS_E_UNSUPPORTED, "an undistort (table) plan is its own lens");
+    if (cam < 0 || cam >= p->fd.n_cams)
+        return mcs::fail(MCS_E_INVALID, "camera %d (0..%d)", cam, p->fd.n_cams - 1);
+    mcs::Lens L;
+    if (K) {
+        if (n_dist < 0 || (n_dist > 0 && !dist)) return mcs::fail(MCS_E_INVALID, "NULL dist");
+        const int rc = mcs::lens_from(K, dist, n_dist, &L);
+        if (rc) return rc;
+    } else if (!((p->kp.lens_mask >> cam) & 1u)) {
+        return MCS_OK;   // none to remove
+    }
+    if (p->prepared) {
+        const Api *A = mcs::rt::api();
+        if (!A) return MCS_E_HIP;
+        DeviceGuard g(A, p->device);
+        release_tables(A, p);
+    }
+    if (K) {
+        p->lens[cam] = L;
+        p->kp.lens_mask |= 1u << cam;
+    } else {
+        p->lens[cam] = mcs::Lens();
+        p->kp.lens_mask &= ~(1u << cam);
+    }
+    p->lens_stale = true;
+    return MCS_OK;
+}
+
+int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const double *uv, int n,
+                      double *xy, double *r2max)
+{
+    mcs::clear_error();
+    if (!K || (n_dist > 0 && !dist) || n < 0 || (n > 0 && (!uv || !xy)))
+        return mcs::fail(MCS_E_INVALID, "NULL K/dist/uv/xy");
+    mcs::Lens L;
+    const int rc = mcs::lens_from(K, dist, n_dist < 0 ? 0 : n_dist, &L);
+    if (rc) return rc;
+    if (r2max) *r2max = L.r2max;
+    for (int i = 0; i < n; i++) {
+        double x = std::nan(""), y = std::nan("");
+        (void)mcs::lens_apply(L, uv[2 * i], uv[2 * i + 1], x, y);
+        xy[2 * i] = x;
+        xy[2 * i + 1] = y;
+    }
     return MCS_OK;
 }
 
@@ -2200,14 +2269,16 @@ int mcs_plan_stats(const mcs_plan *p, int64_t *stats, int n)
 {
     if (!p || !stats) return mcs::fail(MCS_E_INVALID, "NULL plan/stats");
     const int64_t tiles = (int64_t)p->gx * p->gy;
-    const int64_t v[20] = {p->prepared ? 1 : 0, tiles, tiles - p->n_fallback, p->n_fallback,
+    int lens_cams = 0;
+    for (int c = 0; c < MCS_MAX_CAMS; c++) lens_cams += (p->kp.lens_mask >> c) & 1u;
+    const int64_t v[21] = {p->prepared ? 1 : 0, tiles, tiles - p->n_fallback, p->n_fallback,
                            tiles * (int64_t)(sizeof(mcs::TileHdr) +
                                              mcs::kTilePx * (mcs::kDescWords + 1) * 4),
                            p->blend, p->n_blend, p->mb_slots, p->n_degraded, p->n_bands,
                            p->n_bands_lds, p->n_big, p->mb_mixed_px, p->mb_r1,
                            p->dma_bytes, p->box_bytes, p->n_strips, p->sw_px,
-                           (int64_t)mcs::kSwCols * p->sw_jb, p->sw_desc_rows};
-    for (int i = 0; i < n; i++) stats[i] = i < 20 ? v[i] : 0;
+                           (int64_t)mcs::kSwCols * p->sw_jb, p->sw_desc_rows, lens_cams};
+    for (int i = 0; i < n; i++) stats[i] = i < 21 ? v[i] : 0;
     return MCS_OK;
 }
 

@@ -7,6 +7,7 @@
 #include "hip_rt.h"
 #include "mcs.h"
 #include "mcs_kparams.h"
+#include "mcs_lens_core.h"
 
 // Returns MCS_E_HIP with the HIP error text when `expr` fails (needs `A`, the bound runtime).
 #define HIP_TRY(expr)                                                                          \
@@ -28,6 +29,9 @@ int build_flat(const mcs_stage_desc *stages, int n_stages, int cam0_w, int cam0_
 void fill_kparams(const mcs_flat_desc &fd, KParams *kp);
 int block_width(int W, int H);
 bool undistort_map(const double *K, const double *dist, int n_dist, int w, int h, int32_t *tab);
+// Lens (mcs_lens_core.h) of a camera matrix and an OpenCV distortion vector, r2max included;
+// MCS_E_UNSUPPORTED / MCS_E_INVALID for what the model does not cover.
+int lens_from(const double *K, const double *dist, int n_dist, Lens *L);
 // Pairwise graph-cut seam labels over the seam grid (mcs_seam.cpp; spec: oracle/orc_seam.c).
 int seam_graphcut(int n_cams, int gw, int gh, uint8_t *lab, const uint16_t *cov,
                   const uint8_t *smp, int cn);

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "mcs_kparams.h"
+#include "mcs_lens_core.h"
 
 namespace mcs {
 
@@ -39,15 +40,98 @@ __device__ __forceinline__ void map_exact(const KStage &S, int X, int Y, int &xo
     yo = cv_round_clamped((Y0 + S.m[3] * dx1) * W);
 }
 
+// The "far outside" map value: rays behind a cylinder camera, positions beyond a lens' valid
+// radius.
+template <int INTERP>
+__device__ __forceinline__ int map_far()
+{
+    return INTERP == MCS_INTER_LINEAR ? -(1 << 25) : -(1 << 20);
+}
+
+// map_exact's position before the fixed-point scaling, as doubles: the input of a lens.
+__device__ __forceinline__ void map_exact_uv(const KStage &S, int X, int Y, double &u, double &v)
+{
+    const int xb = S.bw_shift >= 0 ? ((X >> S.bw_shift) << S.bw_shift) : (X / S.bw0) * S.bw0;
+    const int x1 = X - xb;
+    const double dxb = (double)xb, dy = (double)Y, dx1 = (double)x1;
+    const double X0 = S.m[0] * dxb + S.m[1] * dy + S.m[2];
+    const double Y0 = S.m[3] * dxb + S.m[4] * dy + S.m[5];
+    const double W0 = S.m[6] * dxb + S.m[7] * dy + S.m[8];
+    const double W = W0 + S.m[6] * dx1;
+    const double Wi = (W != 0.0) ? 1.0 / W : 0.0;
+    u = (X0 + S.m[0] * dx1) * Wi;
+    v = (Y0 + S.m[3] * dx1) * Wi;
+}
+
+// Row `cam` of the lens table.  The table is read-only for every kernel, so it is addressed in
+// the constant address space: a wave-uniform camera index then gives scalar loads.
+__device__ __forceinline__ Lens lens_row(const KParams &P, int cam)
+{
+    typedef __attribute__((address_space(4))) const double cdouble;
+    const cdouble *t = (const cdouble *)P.lens_tab + cam * kLensDoubles;
+    Lens L;
+    L.fx = t[0];
+    L.fy = t[1];
+    L.cx = t[2];
+    L.cy = t[3];
+#pragma unroll
+    for (int i = 0; i < 12; i++) L.k[i] = t[4 + i];
+    L.r2max = t[16];
+    return L;
+}
+
+// Position (u, v) of camera cam's undistorted image through its lens, in map_exact's units of the
+// RAW frame; beyond the valid radius: far outside.
+template <int INTERP>
+__device__ __forceinline__ void lens_map(const KParams &P, int cam, double u, double v, int &xo,
+                                         int &yo)
+{
+    const Lens L = lens_row(P, cam);
+    double xr, yr;
+    if (!lens_apply(L, u, v, xr, yr)) {
+        xo = yo = map_far<INTERP>();
+        return;
+    }
+    const double k = INTERP == MCS_INTER_LINEAR ? 32.0 : 1.0;
+    xo = cv_round_clamped(xr * k);
+    yo = cv_round_clamped(yr * k);
+}
+
+__device__ __forceinline__ bool has_lens(const KParams &P, int cam)
+{
+    return (P.lens_mask >> cam) & 1u;
+}
+
+// Camera 0 of a chain plan (the integer-placed slot) has a lens: its pixels are then mapped
+// (cam0_lens_map), not copied.
+__device__ __forceinline__ bool cam0_lensed(const KParams &P)
+{
+    return (P.lens_mask & 1u) && P.cam0_w > 0;
+}
+
+template <int INTERP>
+__device__ __forceinline__ void cam0_lens_map(const KParams &P, int x, int y, int &xo, int &yo)
+{
+    lens_map<INTERP>(P, 0, (double)(x + P.cam0_offx), (double)(y + P.cam0_offy), xo, yo);
+}
+
 // Source coordinate of output pixel (x, y) under stage S, in map_exact's units.  Cylinder
 // stages (mcs_plan_create_cylindrical): ray (sin t, h, cos t) of the panorama column/row, rotated
 // into the camera (d = R ray, explicit summation order), projected x = f dx / dz + cx; rays
-// behind the camera map far outside every frame.
+// behind the camera map far outside every frame.  A camera with a lens (has_lens): the position
+// in its undistorted image, as a double, goes through lens_map into its raw frame.
 template <int INTERP>
 __device__ __forceinline__ void stage_map(const KParams &P, const KStage &S, int x, int y,
                                           int &xo, int &yo)
 {
+    const bool lens = has_lens(P, S.cam);
     if (S.kind == kStageHomography) {
+        if (lens) {
+            double u, v;
+            map_exact_uv(S, x + S.offx, y + S.offy, u, v);
+            lens_map<INTERP>(P, S.cam, u, v, xo, yo);
+            return;
+        }
         map_exact<INTERP>(S, x + S.offx, y + S.offy, xo, yo);
         return;
     }
@@ -63,10 +147,14 @@ __device__ __forceinline__ void stage_map(const KParams &P, const KStage &S, int
     const double dy = (S.m[3] * sn + S.m[4] * hv) + S.m[5] * cs;
     const double dz = (S.m[6] * sn + S.m[7] * hv) + S.m[8] * cs;
     if (!(dz > 0.0)) {
-        xo = yo = INTERP == MCS_INTER_LINEAR ? -(1 << 25) : -(1 << 20);
+        xo = yo = map_far<INTERP>();
         return;
     }
     const double sx = (S.f * dx) / dz + S.cx, sy = (S.f * dy) / dz + S.cy;
+    if (lens) {
+        lens_map<INTERP>(P, S.cam, sx, sy, xo, yo);
+        return;
+    }
     const double k = INTERP == MCS_INTER_LINEAR ? 32.0 : 1.0;
     xo = cv_round_clamped(sx * k);
     yo = cv_round_clamped(sy * k);

@@ -153,8 +153,19 @@ __device__ __forceinline__ Geo describe_geo(const KParams &P, int x, int y)
     } else if (s < 0) {          // camera 0 pasted whole: a copy (weights 32768, 0, 0, 0)
         sw = P.cam0_w;
         sh = P.cam0_h;
-        X = (x + P.cam0_offx) << 5;
-        Y = (y + P.cam0_offy) << 5;
+        if (cam0_lensed(P)) {    // ... or sampled through its lens, like a stage
+            cam0_lens_map<INTERP>(P, x, y, X, Y);
+            if (INTERP == MCS_INTER_NEAREST) {
+                X = sat_i16(X);
+                Y = sat_i16(Y);
+                const bool in = (unsigned)X < (unsigned)sw && (unsigned)Y < (unsigned)sh;
+                X = in ? X * 32 : -(1 << 20);
+                Y = in ? Y * 32 : -(1 << 20);
+            }
+        } else {
+            X = (x + P.cam0_offx) << 5;
+            Y = (y + P.cam0_offy) << 5;
+        }
     } else {
         sw = sh = X = Y = 0;
     }
@@ -853,21 +864,31 @@ __device__ __forceinline__ void footprint_mark(const KParams &P, uint8_t *const 
             }
         }
     };
+    int X, Y, cam, sw, sh;
     if (s < 0) {
-        mark(0, x + P.cam0_offx, y + P.cam0_offy, P.cam0_w, P.cam0_h);
-        return;
+        if (!cam0_lensed(P)) {
+            mark(0, x + P.cam0_offx, y + P.cam0_offy, P.cam0_w, P.cam0_h);
+            return;
+        }
+        cam = 0;
+        sw = P.cam0_w;
+        sh = P.cam0_h;
+        cam0_lens_map<INTERP>(P, x, y, X, Y);
+    } else {
+        const KStage &S = P.st[s];
+        cam = S.cam;
+        sw = S.src_w;
+        sh = S.src_h;
+        stage_map<INTERP>(P, S, x, y, X, Y);
     }
-    const KStage &S = P.st[s];
-    int X, Y;
-    stage_map<INTERP>(P, S, x, y, X, Y);
     if (INTERP == MCS_INTER_NEAREST) {
-        mark(S.cam, sat_i16(X), sat_i16(Y), S.src_w, S.src_h);
+        mark(cam, sat_i16(X), sat_i16(Y), sw, sh);
     } else {
         const int sx = sat_i16(X >> 5), sy = sat_i16(Y >> 5), fx = X & 31, fy = Y & 31;
-        mark(S.cam, sx, sy, S.src_w, S.src_h);
-        if (fx) mark(S.cam, sx + 1, sy, S.src_w, S.src_h);
-        if (fy) mark(S.cam, sx, sy + 1, S.src_w, S.src_h);
-        if (fx && fy) mark(S.cam, sx + 1, sy + 1, S.src_w, S.src_h);
+        mark(cam, sx, sy, sw, sh);
+        if (fx) mark(cam, sx + 1, sy, sw, sh);
+        if (fy) mark(cam, sx, sy + 1, sw, sh);
+        if (fx && fy) mark(cam, sx + 1, sy + 1, sw, sh);
     }
 }
 

@@ -265,5 +265,29 @@ bool undistort_map(const double *K, const double *dist, int n_dist, int w, int h
     return true;
 }
 
-}  // namespace mcs
+int lens_from(const double *K, const double *dist, int n_dist, Lens *L)
+{
+    if (!(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8 || n_dist == 12 ||
+          n_dist == 14))
+        return fail(MCS_E_UNSUPPORTED, "distortion vector of %d coefficients (0, 4, 5, 8, 12 or 14)",
+                    n_dist);
+    for (int i = 0; i < 9; i++)
+        if (!std::isfinite(K[i])) return fail(MCS_E_INVALID, "K[%d] not finite", i);
+    for (int i = 0; i < n_dist; i++)
+        if (!std::isfinite(dist[i])) return fail(MCS_E_INVALID, "dist[%d] not finite", i);
+    if (K[1] != 0.0 || K[3] != 0.0 || K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0)
+        return fail(MCS_E_UNSUPPORTED, "K must be [[fx 0 cx] [0 fy cy] [0 0 1]] (no skew)");
+    if (K[0] == 0.0 || K[4] == 0.0) return fail(MCS_E_INVALID, "fx / fy is 0");
+    if (n_dist == 14 && (dist[12] != 0.0 || dist[13] != 0.0))
+        return fail(MCS_E_UNSUPPORTED, "sensor tilt (tau_x, tau_y) is not supported");
+    memset(L, 0, sizeof(*L));
+    L->fx = K[0];
+    L->fy = K[4];
+    L->cx = K[2];
+    L->cy = K[5];
+    for (int i = 0; i < n_dist && i < 12; i++) L->k[i] = dist[i];
+    L->r2max = lens_r2max(*L);
+    return MCS_OK;
+}
 
+}  // namespace mcs
