@@ -1318,7 +1318,7 @@ constexpr int mb_lds_wait(int ph, bool first)
 // band's source rows staged in an LDS ring by LDS-DMA, 4 rows per wave instruction (KMbBandArgs
 // bgrp), the windows read from LDS (descriptor .x = the two windows' ring offsets): one 16-byte
 // chunk per lane instead of four 12-byte gathers per lane and row.  Mode 2 needs a band whose
-// source rows advance with its rows (mcs_capi.cpp band_lds_tables checks the ring schedule);
+// source rows advance with its rows (mcs_prepare.cpp band_lds_tables checks the ring schedule);
 // the other bands of an aligned launch take mode 1.  In mode 2 the descriptors come by LDS-DMA
 // too (16 B per lane and row: windows, meta, the offset of the group issued after that row), so
 // the loop holds no ordinary global load: the compiler's own vmcnt waits for ordinary loads

@@ -951,7 +951,7 @@ __device__ __forceinline__ void resize_px(const KResizeArgs &a)
 }  // namespace mcs
 
 // ---------------------------------------------------------------------------------------------
-// Entry points (names looked up by mcs_capi.cpp).  Block shapes: prepare (64, 8, 1) over the tile
+// Entry points (names looked up by mcs_prepare.cpp kernels).  Block shapes: prepare (64, 8, 1) over the tile
 // grid (ceil(out_w/256), ceil(out_h/8)); stream (64, 8, 1) over 8 * ceil(tiles / 8) blocks with
 // lds_stream_bytes(CN) of dynamic LDS; direct (64, 8, 1) over the fallback tile list; footprint
 // (256, 1, 1) with grid

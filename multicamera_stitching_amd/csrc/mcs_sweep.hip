@@ -5,8 +5,8 @@
 //
 // The stitch kernels (mcs_kernels.hip) write every mosaic pixel from its owner camera except the
 // pixels of the sweep's output regions; this kernel writes those.  A strip (MbStrip, built once
-// per plan by mcs_capi.cpp prepare_sweep) is a 128-column window over a run of blend-tile rows
-// around one seam region, with the <= 4 owners whose masks reach its region.  One workgroup per
+// per plan by mcs_sweep_host.cpp prepare_sweep) is a 128-column window over a run of blend-tile
+// rows around one seam region, with the <= 4 owners whose masks reach its region.  One workgroup per
 // (strip, capture), 128 threads per owner, walks the window top to bottom, 4 level-0 rows per step
 // in three phases separated by barriers:
 //

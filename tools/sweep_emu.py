@@ -1,5 +1,5 @@
-"""CPU emulation of the multi-band sweep (tools only): prepare_sweep's strips (mcs_capi.cpp) and
-mcs_sweep.hip's step schedule restated in numpy, checked against the C restatement -- a debugging
+"""CPU emulation of the multi-band sweep (tools only): prepare_sweep's strips (mcs_sweep_host.cpp)
+and mcs_sweep.hip's step schedule restated in numpy, checked against the C restatement -- a debugging
 aid for the kernel's ring / lag logic.  python tools/sweep_emu.py [c0|c1|...]"""
 import os
 import sys
