@@ -271,6 +271,62 @@ int mcs_stitch_direct(mcs_plan *plan, const uint8_t *const *d_cams,
  * byte count): touched_px[i] for i < n_cams.  Runs a one-off marking kernel. */
 int mcs_plan_footprint(mcs_plan *plan, int64_t *touched_px, int n_cams);
 
+/* ---- Exposure gain compensation (the role of OpenCV's detail::GainCompensator) -------------
+ * Cameras on their own auto-exposure differ in brightness; the three steps below measure that in
+ * the overlaps, solve one gain per camera, and apply it.
+ *
+ * Overlap statistics of a chain or cylindrical plan on the 2^step_log2 grid of the mosaic (points
+ * (gx << k, gy << k), the seam finder's grid; step_log2 0..4).  A camera's position at a point is
+ * the blend's (the plan's interpolation, lenses included); it covers the point when that position
+ * lies in its frame; its luminance there is the sum of the channel bytes of the replicate-border
+ * sample (the blend's I_s; also for nearest plans).  N[i * n_cams + j]: points covered by both
+ * camera i and camera j (N[i][i]: by i).  S[(f * n_cams + i) * n_cams + j]: camera i's luminance
+ * in capture f summed over the points of N[i][j].  Integers, so exact whatever the summation
+ * order.  Cameras the mosaic does not use have zero rows and columns; blend mode and seams do
+ * not enter; no gains are applied: the call measures the frames it is given.  d_cams / strides as
+ * mcs_stitch_device; N (n_cams^2) and S (n_frames x n_cams^2) are host arrays; runs on `stream`
+ * (NULL: the plan's own) and synchronises.  The first call per (plan, step) builds a table of the
+ * overlap points on the device (kept until another step is asked for, mcs_plan_set_lens or
+ * mcs_plan_destroy; blend and seam changes keep it); a table over 64 MiB: MCS_E_UNSUPPORTED (use
+ * a larger step).  Single-camera plans (warp / undistort): MCS_E_UNSUPPORTED. */
+int mcs_plan_overlap_stats(mcs_plan *plan, const uint8_t *const *d_cams,
+                           const int64_t *cam_frame_stride, int n_frames, int step_log2,
+                           int64_t *N, int64_t *S, void *stream);
+/* The same for one capture of host frames (sorted-label order, calibrated sizes). */
+int mcs_plan_overlap_stats_host(mcs_plan *plan, const uint8_t *const *cams, int step_log2,
+                                int64_t *N, int64_t *S);
+/* Gains from the statistics of ONE capture (host FP64, no device): the minimiser of Brown &
+ * Lowe's objective as detail::GainCompensator builds it.  With I_ij = S_ij / (channels N_ij) (0
+ * where N_ij = 0): for every i, j: b_i += beta N_ij, A_ii += beta N_ij; for j != i also
+ * A_ii += 2 alpha I_ij^2 N_ij, A_ij -= 2 alpha I_ij I_ji N_ij; A g = b by Gaussian elimination
+ * with partial pivoting.  Cameras with N_ii = 0 stay out of the system and get gain 1.  OpenCV's
+ * constants: alpha = 0.01, beta = 100.  For the mean over a batch of F captures pass the sum of
+ * their S and F * N.  gains: n_cams doubles. */
+int mcs_gain_solve_host(int n_cams, const int64_t *N, const int64_t *S, int channels,
+                        double alpha, double beta, double *gains);
+/* Gains of the plan: one scalar per camera (sorted-label order; n_cams values), acting on the
+ * camera's SOURCE bytes before any sampling: q = clamp(round-half-even(256 g), 1, 65535),
+ * p' = min(255, (p q + 128) >> 8); q = 256 is the identity bit for bit.  A stitch with gains is
+ * by definition the stitch of the pre-gained frames.  NULL disables gains; a non-NULL array
+ * enables them even when every q is 256 (as a lens, an identity gain is never dropped).  The
+ * entry points that own a device copy of the frames apply them there, in place, after the upload
+ * and the resize pre-pass: mcs_stitch_host, mcs_stitch_host_sized, mcs_stream_*.
+ * mcs_stitch_device and mcs_stitch_direct read the caller's frames and never write them: on a
+ * plan with gains they return MCS_E_UNSUPPORTED (apply mcs_gain_apply_device to the frames and
+ * stitch with a plan without gains).  Host-side only; keeps the prepared tables.  A gain that is
+ * not finite and positive: MCS_E_INVALID. */
+int mcs_plan_set_gains(mcs_plan *plan, const double *gains);
+/* q[i] of every camera (256 when gains are disabled) and whether gains are enabled; either
+ * pointer may be NULL. */
+int mcs_plan_gains(const mcs_plan *plan, uint16_t *q, int *enabled);
+/* p' = min(255, (p q + 128) >> 8) over n_frames frames of `bytes` bytes (a scalar gain: any
+ * channel count), frame f at d_src + f * src_frame_stride -> d_dst + f * dst_frame_stride (0 =
+ * bytes).  In place (d_dst == d_src, the same stride) or disjoint; partially overlapping src and
+ * dst: MCS_E_INVALID.  q >= 1.  Enqueued on `stream` of `device`. */
+int mcs_gain_apply_device(const uint8_t *d_src, uint8_t *d_dst, int64_t bytes,
+                          int64_t src_frame_stride, int64_t dst_frame_stride, int n_frames,
+                          uint16_t q, int device, void *stream);
+
 /* ---- Streaming (host frames in, host mosaics out) ---------------------
  * `depth` capture slots, each with pinned host staging and device buffers.  submit: the camera
  * frames (sorted-label order, calibrated sizes, or NULL after filling mcs_stream_input() in
@@ -279,8 +335,12 @@ int mcs_plan_footprint(mcs_plan *plan, int64_t *touched_px, int n_cams);
  * overlap upload, stitch and download.  wait: blocks for that slot's mosaic and copies it to
  * `out` (out_h x out_w x C, dense; NULL: no copy, read mcs_stream_output instead); a slot must
  * be collected before it is reused.  The plan (blend mode included) is fixed for the stream's
- * lifetime; the stream lives on the plan's device.  Zero-copy use: the producer writes the next
- * slot's frames into mcs_stream_input(mcs_stream_next_slot()) and submits NULL, the consumer
+ * lifetime; the stream lives on the plan's device.  Exposure gains (mcs_plan_set_gains): whether
+ * they run is fixed at creation -- a plan with gains enabled gets the gain kernels in every slot's
+ * graph -- while their values are read from the plan at each submit and travel with the capture,
+ * so a capture in flight keeps the gains it was submitted with; a stream created without gains
+ * refuses a submit (MCS_E_INVALID) once the plan carries gains other than the identity.
+ * Zero-copy use: the producer writes the next slot's frames into mcs_stream_input(mcs_stream_next_slot()) and submits NULL, the consumer
  * reads mcs_stream_output(slot) after mcs_stream_wait(slot, NULL) until that slot's next
  * submit -- the pipeline then moves bytes only over PCIe. */
 typedef struct mcs_stream mcs_stream;

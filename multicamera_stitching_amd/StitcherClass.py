@@ -128,7 +128,7 @@ def _plan_key(descs, cam0_shape, channels, interp, device):
 class _Transient(object):
     """Mixin: keeps GPU state (plans, locks) out of pickles and deep copies."""
 
-    _TRANSIENT = ("_mcs_cache", "_mcs_lenses")
+    _TRANSIENT = ("_mcs_cache", "_mcs_lenses", "_mcs_gains")
 
     def __getstate__(self):
         st = dict(self.__dict__)
@@ -300,6 +300,54 @@ class Stitcher(_Transient, Debugger):
             self.__dict__.pop("_mcs_lenses", None)
         return self
 
+    def set_gains(self, gains):
+        """Exposure gains (extension): {label: gain} or None.
+
+        One scalar per camera, applied to its source bytes before any sampling
+        (mcs_plan_set_gains: q = round(256 gain), p' = min(255, (p q + 128) >> 8)), so ``stitch``
+        returns the stitch of the pre-gained frames.  A label left out has gain 1; None (or an
+        empty dict) disables gains.  Kept beside the lenses: not pickled, and set again on the
+        plan whenever it is rebuilt.  A plan with gains refuses the device entry points
+        (``plan().stitch_device``): they never write the caller's frames.
+        """
+        labels = [str(l) for l in self.img_labels]
+        table = {}
+        for label, g in dict(gains or {}).items():
+            if str(label) not in labels:
+                raise KeyError("no camera labelled {!r}".format(label))
+            g = float(g)
+            if not (np.isfinite(g) and g > 0.0):
+                raise ValueError("gain of camera {!r} must be finite and positive".format(label))
+            table[labels.index(str(label))] = g
+        if table:
+            self.__dict__["_mcs_gains"] = table
+        else:
+            self.__dict__.pop("_mcs_gains", None)
+        return self
+
+    def compensate_exposure(self, images_dic, step_log2=2, alpha=0.01, beta=100.0):
+        """Measure one capture's brightness differences in the overlaps and set the gains that
+        even them out (the role of OpenCV's detail::GainCompensator): overlap statistics on the
+        2^step_log2 grid of the mosaic (mcs_plan_overlap_stats_host; the frames as given, no
+        gains applied), Brown & Lowe's solve (mcs_gain_solve_host), then ``set_gains``.  Frames
+        at their calibrated sizes.  Returns {label: gain}."""
+        cams = [images_dic[label] for label in self.img_labels]
+        cams, cam0_hw, _ = _conform_cameras(self, self.stitchers, cams)
+        if cam0_hw is None:
+            raise ValueError("no calibrated stage: nothing overlaps")
+        cache = self._cache()
+        with cache.lock:
+            plan = _get_plan(self, self.stitchers, cam0_hw, _channels(cams[0]))
+            for i, (c, (h, w)) in enumerate(zip(cams, plan.cam_shapes)):
+                if tuple(c.shape[:2]) != (h, w):
+                    raise ValueError("camera {!r}: frame {}x{}, calibrated {}x{}".format(
+                        self.img_labels[i], c.shape[1], c.shape[0], w, h))
+            N, S = plan.overlap_stats_host(cams, step_log2)
+        g = _capi.gain_solve(N, S, plan.channels, alpha, beta)
+        gains = {label: float(g[i]) for i, label in enumerate(self.img_labels)}
+        self.set_gains(gains)
+        return gains
+
 
 # =============================================================================================
 class StitcherBase(_Transient, Debugger):
@@ -433,7 +481,15 @@ def _get_plan(owner, chain, cam0_shape, channels, interp=None, device=None):
         for i, (k, d) in sorted(lenses.items()):
             plan.set_lens(i, k, d)
         return plan
-    return cache.get(key, make)
+    plan = cache.get(key, make)
+    # Stitcher.set_gains: host-side state of the plan (no table depends on it), so it is not
+    # part of the key; set on every fetch, a rebuilt plan included
+    gains = owner.__dict__.get("_mcs_gains")
+    if gains:
+        plan.set_gains([gains.get(i, 1.0) for i in range(plan.n_cams)])
+    elif plan.gains()[1]:
+        plan.set_gains(None)
+    return plan
 
 
 def _conform_cameras(owner, chain, cams):

@@ -51,7 +51,9 @@ EXPORTS = (
     "mcs_rig_job_submit", "mcs_rig_job_wait", "mcs_rig_job_counts", "mcs_rig_job_destroy",
     "mcs_seam_graphcut_device", "mcs_plan_seam_stats", "mcs_chain_stages",
     "mcs_rig_job_wait_stitch", "mcs_rig_job_create_batch", "mcs_rig_job_wait_stitch_batch",
-    "mcs_plan_set_lens", "mcs_lens_map_host",
+    "mcs_plan_set_lens", "mcs_lens_map_host", "mcs_plan_overlap_stats",
+    "mcs_plan_overlap_stats_host", "mcs_gain_solve_host", "mcs_plan_set_gains", "mcs_plan_gains",
+    "mcs_gain_apply_device",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -288,6 +290,19 @@ def load() -> ctypes.CDLL:
         L.mcs_plan_stats.restype = I
         L.mcs_plan_footprint.argtypes = [P, ctypes.POINTER(ctypes.c_int64), I]
         L.mcs_plan_footprint.restype = I
+        L.mcs_plan_overlap_stats.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(i64), I, I, P, P,
+                                             P]
+        L.mcs_plan_overlap_stats.restype = I
+        L.mcs_plan_overlap_stats_host.argtypes = [P, ctypes.POINTER(P), I, P, P]
+        L.mcs_plan_overlap_stats_host.restype = I
+        L.mcs_gain_solve_host.argtypes = [I, P, P, I, ctypes.c_double, ctypes.c_double, P]
+        L.mcs_gain_solve_host.restype = I
+        L.mcs_plan_set_gains.argtypes = [P, P]
+        L.mcs_plan_set_gains.restype = I
+        L.mcs_plan_gains.argtypes = [P, P, ctypes.POINTER(I)]
+        L.mcs_plan_gains.restype = I
+        L.mcs_gain_apply_device.argtypes = [P, P, i64, i64, i64, I, ctypes.c_uint16, I, P]
+        L.mcs_gain_apply_device.restype = I
         L.mcs__force_off64.argtypes = [I]   # test hook (not part of mcs.h)
         L.mcs__force_off64.restype = None
         if L.mcs_abi_version() != ABI_VERSION:
@@ -541,6 +556,53 @@ class Plan:
                                           int(d.size)))
         return self
 
+    def overlap_stats(self, cam_ptrs, cam_frame_strides, n_frames: int, step_log2: int = 2,
+                      stream: int = 0):
+        """mcs_plan_overlap_stats on device-resident captures (raw device pointers): (N, S),
+        int64 arrays of shape (n_cams, n_cams) and (n_frames, n_cams, n_cams).  N[i, j]: grid
+        points both cameras cover; S[f, i, j]: camera i's luminance over them in capture f."""
+        n = self.n_cams
+        ptrs = (ctypes.c_void_p * n)(*[int(p) if p else None for p in cam_ptrs])
+        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
+        N = np.zeros((n, n), np.int64)
+        S = np.zeros((max(int(n_frames), 0), n, n), np.int64)
+        check(self._lib.mcs_plan_overlap_stats(self._h, ptrs, strides, int(n_frames),
+                                               int(step_log2), N.ctypes.data, S.ctypes.data,
+                                               ctypes.c_void_p(int(stream))))
+        return N, S
+
+    def overlap_stats_host(self, cams, step_log2: int = 2):
+        """mcs_plan_overlap_stats_host: one capture of host frames (sorted-label order,
+        calibrated sizes) -> (N, S), both (n_cams, n_cams) int64."""
+        cams = [np.ascontiguousarray(c, dtype=np.uint8) for c in cams]
+        ptrs = (ctypes.c_void_p * len(cams))(*[c.ctypes.data for c in cams])
+        n = self.n_cams
+        N = np.zeros((n, n), np.int64)
+        S = np.zeros((n, n), np.int64)
+        check(self._lib.mcs_plan_overlap_stats_host(self._h, ptrs, int(step_log2), N.ctypes.data,
+                                                    S.ctypes.data))
+        return N, S
+
+    def set_gains(self, gains):
+        """mcs_plan_set_gains: one gain per camera (sorted-label order) on its source bytes, or
+        None to disable gains."""
+        if gains is None:
+            check(self._lib.mcs_plan_set_gains(self._h, None))
+            return self
+        g = np.ascontiguousarray(np.asarray(gains, np.float64).reshape(-1))
+        if g.size != self.n_cams:
+            raise ValueError(f"{g.size} gains for a plan of {self.n_cams} cameras")
+        check(self._lib.mcs_plan_set_gains(self._h, g.ctypes.data))
+        return self
+
+    def gains(self):
+        """(q, enabled): the quantised gains (1/256 units, uint16 per camera; 256 when gains
+        are disabled) and whether gains are enabled."""
+        q = np.zeros(self.n_cams, np.uint16)
+        on = ctypes.c_int(0)
+        check(self._lib.mcs_plan_gains(self._h, q.ctypes.data, ctypes.byref(on)))
+        return q, bool(on.value)
+
     def footprint(self):
         arr = (ctypes.c_int64 * MCS_MAX_CAMS)()
         check(self._lib.mcs_plan_footprint(self._h, arr, MCS_MAX_CAMS))
@@ -557,6 +619,33 @@ def resize_linear_device(src_ptr: int, src_w: int, src_h: int, dst_ptr: int, dst
         src_ptr, src_w, src_h, src_pitch or src_w * channels, src_frame_stride, dst_ptr, dst_w,
         dst_h, dst_pitch or dst_w * channels, dst_frame_stride, channels, n_frames, device,
         stream or None))
+
+
+def gain_solve(N, S, channels: int, alpha: float = 0.01, beta: float = 100.0) -> np.ndarray:
+    """mcs_gain_solve_host: the gains (float64 per camera) minimising Brown & Lowe's objective
+    for the overlap statistics N, S of ONE capture (for a batch mean pass S.sum(0) and F * N).
+    alpha, beta: OpenCV's GainCompensator constants."""
+    N = np.ascontiguousarray(N, dtype=np.int64)
+    S = np.ascontiguousarray(S, dtype=np.int64)
+    n = N.shape[0]
+    if N.shape != (n, n) or S.shape != (n, n):
+        raise ValueError(f"N {N.shape} and S {S.shape} must both be (n_cams, n_cams)")
+    g = np.ones(n, np.float64)
+    check(load().mcs_gain_solve_host(n, N.ctypes.data, S.ctypes.data, int(channels),
+                                     float(alpha), float(beta), g.ctypes.data))
+    return g
+
+
+def gain_apply_device(src_ptr: int, dst_ptr: int, nbytes: int, q: int, n_frames: int = 1,
+                      src_frame_stride: int = 0, dst_frame_stride: int = 0, device: int = 0,
+                      stream: int = 0):
+    """mcs_gain_apply_device: p' = min(255, (p q + 128) >> 8) on device-resident bytes (q: the
+    gain in 1/256, as Plan.gains() reports it); in place when dst_ptr == src_ptr."""
+    if not 0 <= int(q) <= 65535:
+        raise ValueError(f"q {q} outside 0..65535")
+    check(load().mcs_gain_apply_device(src_ptr, dst_ptr, int(nbytes), int(src_frame_stride),
+                                       int(dst_frame_stride), int(n_frames), int(q), int(device),
+                                       stream or None))
 
 
 def match_hamming_knn2(query, train, device: int = 0):

@@ -21,7 +21,8 @@ using namespace mcs::host;
 using mcs::DeviceGuard;
 using mcs::kMaxDevices;
 
-namespace {
+namespace mcs {
+namespace host {
 
 int ensure_stream(const Api *A, mcs_plan *p)
 {
@@ -44,7 +45,8 @@ int ensure_host_buffers(const Api *A, mcs_plan *p)
     return MCS_OK;
 }
 
-}  // namespace
+}  // namespace host
+}  // namespace mcs
 
 extern "C" {
 
@@ -268,7 +270,7 @@ int mcs_plan_destroy(mcs_plan *p)
 {
     if (!p) return MCS_OK;
     bool touched = p->stream || p->d_out || !p->t.owned.empty() || p->side || p->side2 ||
-                   p->d_lens || p->d_cyl || p->d_map || p->d_seam;
+                   p->d_lens || p->d_cyl || p->d_map || p->d_seam || p->ov.d_table || p->ov.d_S;
     for (int i = 0; i < MCS_MAX_CAMS; i++) touched = touched || p->d_cams[i];
     if (touched) {
         const Api *A = mcs::rt::api();
@@ -281,6 +283,7 @@ int mcs_plan_destroy(mcs_plan *p)
             for (int i = 0; i < MCS_MAX_CAMS; i++)
                 if (p->d_raw[i]) (void)A->hipFree(p->d_raw[i]);
             release_tables(A, p);
+            drop_overlap(A, p);
             if (p->d_cyl) (void)A->hipFree(p->d_cyl);
             if (p->d_seam) (void)A->hipFree(p->d_seam);
             if (p->d_map) (void)A->hipFree(p->d_map);
@@ -350,9 +353,17 @@ int mcs_stitch_host_sized(mcs_plan *p, const uint8_t *const *cams, const int *ca
         const int cw = p->fd.cam_w[i], ch = p->fd.cam_h[i];
         const int w = cam_w ? cam_w[i] : cw, h = cam_h ? cam_h[i] : ch;
         if (w <= 0 || h <= 0) return mcs::fail(MCS_E_INVALID, "cams[%d] size %dx%d", i, w, h);
+        // exposure gains act on the frame the stitch samples: after the upload and the resize
+        const auto gain = [&]() {
+            if (!p->gains_on) return (int)MCS_OK;
+            return launch_gain(A, k, p->d_cams[i], p->d_cams[i], (int64_t)cw * ch * C, 0, 0, 1,
+                               p->gain_q[i], nullptr, p->stream);
+        };
         if (w == cw && h == ch) {
             HIP_TRY(A->hipMemcpyAsync(p->d_cams[i], cams[i], (size_t)cw * ch * C,
                                       hipMemcpyHostToDevice, p->stream));
+            rc = gain();
+            if (rc) return rc;
             continue;
         }
         const size_t bytes = (size_t)w * h * C;
@@ -369,6 +380,7 @@ int mcs_stitch_host_sized(mcs_plan *p, const uint8_t *const *cams, const int *ca
         HIP_TRY(A->hipMemcpyAsync(p->d_raw[i], cams[i], bytes, hipMemcpyHostToDevice, p->stream));
         rc = launch_resize(A, k, p->d_raw[i], w, h, (int64_t)w * C, 0, p->d_cams[i], cw, ch,
                            (int64_t)cw * C, 0, C, 1, p->stream);
+        if (rc == MCS_OK) rc = gain();
         if (rc) return rc;
     }
     mcs::KParams kp = p->kp;
@@ -443,9 +455,30 @@ static int device_kparams(const mcs_plan *p, const uint8_t *const *d_cams,
     return MCS_OK;
 }
 
+// The device entry points read caller memory and never write it, so they cannot apply gains.
+static int refuse_gains(const mcs_plan *p, const char *entry)
+{
+    if (!p || !p->gains_on) return MCS_OK;
+    return mcs::fail(MCS_E_UNSUPPORTED, "%s reads the caller's frames and never writes them: on a "
+                     "plan with gains (mcs_plan_set_gains) apply them to the frames first with "
+                     "mcs_gain_apply_device and stitch with a plan without gains", entry);
+}
+
 int mcs_stitch_device(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
                       uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,
                       void *stream)
+{
+    const int rc = refuse_gains(p, "mcs_stitch_device");
+    if (rc) return rc;
+    return mcs::stitch_device_frames(p, d_cams, cam_frame_stride, d_out, out_pitch,
+                                     out_frame_stride, n_frames, stream);
+}
+
+}  // extern "C"
+
+int mcs::stitch_device_frames(mcs_plan *p, const uint8_t *const *d_cams,
+                              const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                              int64_t out_frame_stride, int n_frames, void *stream)
 {
     mcs::KParams kp;
     int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
@@ -459,13 +492,17 @@ int mcs_stitch_device(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *
     return launch_stitch(A, p, kp, n_frames, (hipStream_t)stream);
 }
 
+extern "C" {
+
 int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
                       uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,
                       void *stream)
 {
     mcs::KParams kp;
-    int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                            n_frames, &kp);
+    int rc = refuse_gains(p, "mcs_stitch_direct");
+    if (rc) return rc;
+    rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride, n_frames,
+                        &kp);
     if (rc) return rc;
     if (p->blend != MCS_BLEND_NONE && p->blend != MCS_BLEND_SEAM)
         return mcs::fail(MCS_E_UNSUPPORTED, "mcs_stitch_direct renders paste / seam plans; "
@@ -578,6 +615,12 @@ int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist,
         if (!A) return MCS_E_HIP;
         DeviceGuard g(A, p->device);
         release_tables(A, p);
+    }
+    if (p->ov.d_table || p->ov.d_S) {   // the overlap table holds positions through the lenses
+        const Api *A = mcs::rt::api();
+        if (!A) return MCS_E_HIP;
+        DeviceGuard g(A, p->device);
+        drop_overlap(A, p);
     }
     if (K) {
         p->lens[cam] = L;

@@ -17,6 +17,7 @@
 #include "mcs_dev.h"
 
 #include "mcs_blend.h"
+#include "mcs_gain.h"
 
 namespace mcs {
 
@@ -1161,4 +1162,29 @@ extern "C" __global__ __launch_bounds__(256) void mcs_footprint_i1(const mcs::KP
                                                                    unsigned long long *counts)
 {
     mcs::footprint_mark<1, 1>(P, masks, counts);
+}
+
+// Exposure compensation (mcs_gain.h): the overlap table (once per plan and grid step), the
+// overlap sums (per batch of captures) and the gain on a camera's source bytes.
+#define MCS_OVERLAP_PREP_ENTRY(IN)                                                             \
+    extern "C" __global__ __launch_bounds__(256) void mcs_overlap_prep_i##IN(                  \
+        const mcs::KOverlapPrepArgs a)                                                         \
+    {                                                                                          \
+        mcs::overlap_prep<IN>(a);                                                              \
+    }
+MCS_OVERLAP_PREP_ENTRY(0)
+MCS_OVERLAP_PREP_ENTRY(1)
+#define MCS_OVERLAP_SUM_ENTRY(CN)                                                              \
+    extern "C" __global__ __launch_bounds__(256) void mcs_overlap_sum_c##CN(                   \
+        const mcs::KOverlapSumArgs a)                                                          \
+    {                                                                                          \
+        mcs::overlap_sum<CN>(a);                                                               \
+    }
+MCS_OVERLAP_SUM_ENTRY(1)
+MCS_OVERLAP_SUM_ENTRY(2)
+MCS_OVERLAP_SUM_ENTRY(3)
+MCS_OVERLAP_SUM_ENTRY(4)
+extern "C" __global__ __launch_bounds__(256) void mcs_gain_apply(const mcs::KGainArgs a)
+{
+    mcs::gain_apply(a);
 }

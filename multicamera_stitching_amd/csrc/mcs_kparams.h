@@ -433,4 +433,60 @@ struct KSeamArgs {
     int gw, gh, k, pad_;
 };
 
+// ---- Exposure compensation (mcs_gain.h, mcs_gain.cpp) ---------------------------------------
+// Overlap table of a plan at one grid step (mcs_plan_overlap_stats): the grid points every camera
+// pair covers together, grouped into one segment per pair (i < j: 16-byte entries, the two
+// cameras' (x32, y32), lower camera first) and one per camera (the diagonal: 8-byte entries, the
+// camera's own (x32, y32)).  Segment (i, j) is row i * MCS_MAX_CAMS + j of the count / offset
+// arrays.  Built in two passes of mcs_overlap_prep_i*: count (mode 0), then -- after the host's
+// prefix sum over the counts -- fill (mode 1).
+constexpr int kOvSegs = MCS_MAX_CAMS * MCS_MAX_CAMS;
+constexpr int kOvPrepThreads = 256;
+struct KOverlapPrepArgs {
+    KParams P;
+    uint32_t *count;               // [kOvSegs] entries per segment (mode 0 adds, = N)
+    uint32_t *cursor;              // [kOvSegs] fill positions (mode 1 adds; zeroed before)
+    const int64_t *seg_off;        // [kOvSegs] byte offset of each segment in table (mode 1)
+    uint8_t *table;
+    int gw, gh, k, mode;
+};
+// The sums (mcs_overlap_sum_c*): a block of kOvSumThreads lanes walks one unit -- up to
+// kOvUnitEntries consecutive entries of one segment -- for kOvFrames captures (grid y), the two
+// cameras' sums per capture in registers; partials are 32-bit (kOvUnitEntries * 4 * 255 < 2^31),
+// the accumulators S 64-bit.
+constexpr int kOvSumThreads = 256;
+constexpr int kOvLaneEntries = 8;
+constexpr int kOvUnitEntries = kOvSumThreads * kOvLaneEntries;
+constexpr int kOvFrames = 4;       // captures per block (positions loaded once per entry)
+struct OvUnit {
+    int64_t off;                   // byte offset of the unit's first entry in the table
+    int cam_a, cam_b;              // cam_a == cam_b: a diagonal segment (8-byte entries)
+    int n;                         // entries (1..kOvUnitEntries)
+    int pad_;
+};
+static_assert(sizeof(OvUnit) == 24, "OvUnit layout");
+struct KOverlapSumArgs {
+    const uint8_t *cams[MCS_MAX_CAMS];
+    int64_t cam_fstride[MCS_MAX_CAMS];
+    int cam_w[MCS_MAX_CAMS], cam_h[MCS_MAX_CAMS];
+    const uint8_t *table;
+    const OvUnit *units;
+    unsigned long long *S;         // [n_frames][n_cams][n_cams], zeroed before the launch
+    int n_cams, n_frames;
+};
+
+// Gain of one camera on its source bytes (mcs_gain_apply): p' = min(255, (p q + 128) >> 8), q the
+// gain in 1/256 (256 = identity).  grid (chunks of kGainChunk bytes, frames), block kGainThreads.
+constexpr int kGainThreads = 256;
+constexpr int kGainVecs = 4;       // 16-byte vectors per lane
+constexpr int kGainChunk = kGainThreads * kGainVecs * 16;
+struct KGainArgs {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t bytes, src_fstride, dst_fstride;
+    const uint16_t *q_tab;         // device q of this camera (streams: refreshed per submit), or
+    uint32_t q;                    // NULL: the value q
+    int pad_;
+};
+
 }  // namespace mcs

@@ -140,6 +140,23 @@ struct mcs_plan {
     mcs::Lens lens[MCS_MAX_CAMS] = {};
     double *d_lens = nullptr;
     bool lens_stale = false;
+    // exposure gains (mcs_plan_set_gains): q = the gain in 1/256 per camera; enabled by any
+    // non-NULL array, identity included.  Host state only: the prepared tables do not depend on it.
+    bool gains_on = false;
+    uint16_t gain_q[MCS_MAX_CAMS] = {};
+    // overlap table of mcs_plan_overlap_stats (mcs_gain.cpp), built for grid step ov.step.  Not
+    // part of Tables: it depends on the geometry and the lenses only, so blend and seam changes
+    // keep it; mcs_plan_set_lens and mcs_plan_destroy drop it (drop_overlap).
+    struct Overlap {
+        int step = -1;                    // -1: none
+        uint8_t *d_table = nullptr;       // segments, then the units (one allocation)
+        mcs::OvUnit *d_units = nullptr;
+        int n_units = 0;
+        int64_t table_bytes = 0;
+        int64_t N[MCS_MAX_CAMS * MCS_MAX_CAMS] = {};   // [i * MCS_MAX_CAMS + j]
+        unsigned long long *d_S = nullptr;             // the sums' accumulators (grown on demand)
+        size_t s_bytes = 0;
+    } ov;
 };
 
 namespace mcs {
@@ -168,6 +185,9 @@ struct Kernels {
     // multi-band sweep (module kModSweep): [channels][dword-aligned windows][2 / 4 owners]
     hipFunction_t mb_sweep[4][2][2] = {};
     hipFunction_t mb_sweep_desc[4][2] = {};   // [channels][interp]
+    hipFunction_t overlap_prep[2] = {};   // [interp]
+    hipFunction_t overlap_sum[5] = {};    // [channels]
+    hipFunction_t gain_apply = nullptr;
 };
 
 // mcs_prepare.cpp
@@ -180,6 +200,20 @@ int upload_plan_tables(const Api *A, mcs_plan *p, hipStream_t s);
 int prepare(const Api *A, mcs_plan *p, hipStream_t s);
 // Frees the prepared tables (they are rebuilt on next use): p->t is a fresh Tables afterwards.
 void release_tables(const Api *A, mcs_plan *p);
+
+// mcs_capi.cpp
+// The plan's own stream and the device buffers of the host-array path, created on first use.
+int ensure_stream(const Api *A, mcs_plan *p);
+int ensure_host_buffers(const Api *A, mcs_plan *p);
+
+// mcs_gain.cpp
+// Frees the overlap table and its accumulators (the next mcs_plan_overlap_stats rebuilds them).
+void drop_overlap(const Api *A, mcs_plan *p);
+// q[cam] on `bytes` source bytes of n_frames frames (in place when dst == src); d_q: a device q
+// read at run time instead (streams).
+int launch_gain(const Api *A, const Kernels *k, const uint8_t *src, uint8_t *dst, int64_t bytes,
+                int64_t src_fstride, int64_t dst_fstride, int n_frames, uint32_t q,
+                const uint16_t *d_q, hipStream_t s);
 
 // mcs_sweep_host.cpp
 int prepare_sweep(const Api *A, mcs_plan *p, const Kernels *k, hipStream_t s);

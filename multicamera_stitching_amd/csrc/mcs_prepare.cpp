@@ -89,6 +89,13 @@ int kernels(const Api *A, int device, const Kernels **out)
         if (rc == MCS_OK) rc = fn("mcs_blend_owner_i0", &k.blend_owner[0]);
         if (rc == MCS_OK) rc = fn("mcs_blend_owner_i1", &k.blend_owner[1]);
         if (rc == MCS_OK) rc = fn("mcs_blend_classify", &k.blend_classify);
+        if (rc == MCS_OK) rc = fn("mcs_overlap_prep_i0", &k.overlap_prep[0]);
+        if (rc == MCS_OK) rc = fn("mcs_overlap_prep_i1", &k.overlap_prep[1]);
+        for (int c = 1; c <= 4 && rc == MCS_OK; c++) {
+            snprintf(name, sizeof(name), "mcs_overlap_sum_c%d", c);
+            rc = fn(name, &k.overlap_sum[c]);
+        }
+        if (rc == MCS_OK) rc = fn("mcs_gain_apply", &k.gain_apply);
         if (rc) return rc;
         k.loaded = true;
     }

@@ -2,7 +2,9 @@
 // double-(or deeper-)buffered pinned staging, H2D on one copy stream, the stitch (captured once
 // per slot into a hipGraph) on the compute stream, D2H on a second copy stream, so that the
 // upload of capture i+1, the stitch of capture i and the download of capture i-1 overlap.  Uses
-// only the public plan API (mcs_stitch_device) plus the bound HIP runtime.
+// the public plan API, the bound HIP runtime and, for the stitch of its own slot buffers,
+// mcs::stitch_device_frames (a plan with gains refuses mcs_stitch_device: the stream applies the
+// gains to its slot's frames itself, as part of the slot's graph).
 #include <sched.h>
 
 #include <cstdio>
@@ -192,6 +194,12 @@ struct mcs_stream {
     size_t cam_off[MCS_MAX_CAMS] = {};
     size_t in_bytes = 0, out_bytes = 0;
     int out_w = 0, out_h = 0;
+    // the plan had gains enabled at creation: every slot's staging ends in a q table (one u16 per
+    // camera at q_off), filled from the plan's current q at submit and uploaded with the frames,
+    // and the gain kernels of the slot read their q from the slot's device copy -- so a capture in
+    // flight keeps the gains it was submitted with and no graph is ever re-instantiated
+    bool gains = false;
+    size_t q_off = 0;
     hipStream_t up = nullptr, compute = nullptr, down = nullptr;
     struct Slot {
         uint8_t *h_in = nullptr, *h_out = nullptr, *d_in = nullptr, *d_out = nullptr;
@@ -213,9 +221,18 @@ int stitch_slot(mcs_stream *s, int i, hipStream_t st)
         cams[c] = s->slot[i].d_in + s->cam_off[c];
         strides[c] = (int64_t)s->cam_w[c] * s->cam_h[c] * s->channels;
     }
+    if (s->gains) {
+        const uint16_t *d_q = reinterpret_cast<const uint16_t *>(s->slot[i].d_in + s->q_off);
+        for (int c = 0; c < s->n_cams; c++) {
+            uint8_t *frame = s->slot[i].d_in + s->cam_off[c];
+            const int rc = mcs::gain_apply_frames(s->plan, frame, frame, strides[c], 0, 0, 1, 256,
+                                                  d_q + c, st);
+            if (rc) return rc;
+        }
+    }
     const int64_t pitch = (int64_t)s->out_w * s->channels;
-    return mcs_stitch_device(s->plan, cams, strides, s->slot[i].d_out, pitch,
-                             pitch * s->out_h, 1, st);
+    return mcs::stitch_device_frames(s->plan, cams, strides, s->slot[i].d_out, pitch,
+                                     pitch * s->out_h, 1, st);
 }
 
 void release(const Api *A, mcs_stream *s)
@@ -250,6 +267,13 @@ int build(const Api *A, mcs_stream *s)
         HIP_TRY(A->hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
         HIP_TRY(A->hipEventCreateWithFlags(&sl.ev_k, hipEventDisableTiming));
         HIP_TRY(A->hipEventCreateWithFlags(&sl.ev_out, hipEventDisableTiming));
+        if (s->gains) {   // identity q until the first submit (the plain run below reads it)
+            uint16_t *q = reinterpret_cast<uint16_t *>(sl.h_in + s->q_off);
+            for (int c = 0; c < MCS_MAX_CAMS; c++) q[c] = 256;
+            HIP_TRY(A->hipMemcpyAsync(sl.d_in + s->q_off, q, MCS_MAX_CAMS * sizeof(uint16_t),
+                                      hipMemcpyHostToDevice, s->up));
+            HIP_TRY(A->hipStreamSynchronize(s->up));
+        }
     }
     // tables, modules and side streams exist before any capture: one plain run
     int rc = mcs_plan_prepare(s->plan, s->compute);
@@ -315,6 +339,17 @@ int mcs_stream_create(mcs_plan *plan, int depth, int use_graphs, mcs_stream **ou
         s->cam_off[c] = s->in_bytes;
         s->in_bytes += ((size_t)fd.cam_w[c] * fd.cam_h[c] * fd.channels + 255) & ~(size_t)255;
     }
+    int gains_on = 0;
+    rc = mcs_plan_gains(plan, nullptr, &gains_on);
+    if (rc) {
+        delete s;
+        return rc;
+    }
+    s->gains = gains_on != 0;
+    if (s->gains) {
+        s->q_off = s->in_bytes;
+        s->in_bytes += 256;
+    }
     s->out_w = fd.out_w;
     s->out_h = fd.out_h;
     s->out_bytes = (size_t)fd.out_w * fd.out_h * fd.channels;
@@ -369,6 +404,23 @@ int mcs_stream_submit_strided(mcs_stream *s, const uint8_t *const *cams,
     mcs_stream::Slot &sl = s->slot[i];
     if (sl.busy)
         return mcs::fail(MCS_E_INVALID, "slot %d not yet collected (call mcs_stream_wait)", i);
+    {
+        // the gains this capture carries: the plan's current q.  Whether gains run at all was
+        // fixed when the stream was created (the kernels are part of the slots' graphs).
+        uint16_t q[MCS_MAX_CAMS] = {};
+        int on = 0;
+        const int rc = mcs_plan_gains(s->plan, q, &on);
+        if (rc) return rc;
+        if (s->gains) {
+            memcpy(sl.h_in + s->q_off, q, sizeof(q));   // (256 each once gains are disabled)
+        } else if (on) {
+            for (int c = 0; c < s->n_cams; c++)
+                if (q[c] != 256)
+                    return mcs::fail(MCS_E_INVALID, "the plan got gains after this stream was "
+                                     "created without them: create the stream from a plan with "
+                                     "gains enabled (mcs_plan_set_gains)");
+        }
+    }
     mcs::DeviceGuard g(A, s->device);
     if (cams) {   // else: the caller filled mcs_stream_input() buffers in place
         // (a camera inside a wider frame, e.g. the main_stream layout with cameras side by side

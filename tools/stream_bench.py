@@ -52,17 +52,20 @@ def host_copy_gbs(nbytes, reps=10):
     return round(reps * nbytes / (time.perf_counter() - t0) / 1e9, 2)
 
 
-def run(w, h, blend, depth, frames, graphs=True, zero_copy=False, link=None):
+def run(w, h, blend, depth, frames, graphs=True, zero_copy=False, link=None, gains=False):
     """zero_copy: frames written into the pinned slots in place (input_views, once per slot:
     a producer decoding straight into them) and mosaics read from the pinned slots
     (wait(copy=False)); otherwise numpy frames in, numpy mosaics out (two host memcpys per
-    capture on the submitting thread)."""
+    capture on the submitting thread).  gains: the plan has exposure gains (mcs_plan_set_gains),
+    so every slot's graph starts with the gain kernels over its frames."""
     from multicamera_stitching_amd import _capi, rig
     from multicamera_stitching_amd.StitcherClass import _stage_desc
     st, images, _ = rig.calibrated_stitcher(4, w, h, 3, seed=0)
     cams = [images[label] for label in st.img_labels]
     plan = _capi.Plan([_stage_desc(sb) for sb in st.stitchers], w, h, 3, 1)
     plan.set_blend(blend)
+    if gains:
+        plan.set_gains([1.06, 0.97, 1.02, 0.94])
     pipe = _capi.StreamPipeline(plan, depth=depth, use_graphs=graphs)
     out = [np.empty(plan.out_shape(), np.uint8) for _ in range(depth)]
     if zero_copy:
@@ -100,7 +103,8 @@ def run(w, h, blend, depth, frames, graphs=True, zero_copy=False, link=None):
     in_mb = sum(c.nbytes for c in cams) / 1e6
     gbs = frames * (in_mb + mpix * 3) / dt / 1e3
     res = {"cams": f"4x{w}x{h}x3", "blend": blend, "depth": depth, "graphs": graphs,
-           "zero_copy": zero_copy, "frames": frames, "fps": round(frames / dt, 1),
+           "zero_copy": zero_copy, "gains": gains, "frames": frames,
+           "fps": round(frames / dt, 1),
            "mpix_per_s": round(frames * mpix / dt, 1), "pcie_gb_per_s": round(gbs, 2)}
     if link is not None:
         res["link_ceiling_gbs"] = link["bidir_gbs"]
@@ -114,6 +118,9 @@ if __name__ == "__main__":
     ap.add_argument("--sizes", default="1920x1080,3840x2160")
     ap.add_argument("--summary", action="store_true",
                     help="also print one closing JSON line holding every configuration's line")
+    ap.add_argument("--gains", action="store_true",
+                    help="every configuration twice, without and with exposure gains on the "
+                         "plan (same build, same box): what the gain kernels cost the stream")
     a = ap.parse_args()
     import torch
     torch.cuda.set_device(0)
@@ -128,9 +135,10 @@ if __name__ == "__main__":
         lines.append({"link_probe": link})
         for blend in (0, 2):
             for depth, graphs, zc in ((1, False, False), (3, True, False), (3, True, True)):
-                r = run(w, h, blend, depth, a.frames, graphs, zc, link)
-                print(json.dumps(r), flush=True)
-                lines.append(r)
+                for gains in ((False, True) if a.gains else (False,)):
+                    r = run(w, h, blend, depth, a.frames, graphs, zc, link, gains)
+                    print(json.dumps(r), flush=True)
+                    lines.append(r)
     if a.summary:
         print(json.dumps({"metric": "streamed rig captures/s (C5: host frames in, host mosaics "
                                     "out, mcs_stream_*)", "unit": "fps", "lines": lines}))
