@@ -313,9 +313,26 @@ int mcs_gain_solve_host(int n_cams, const int64_t *N, const int64_t *S, int chan
  * and the resize pre-pass: mcs_stitch_host, mcs_stitch_host_sized, mcs_stream_*.
  * mcs_stitch_device and mcs_stitch_direct read the caller's frames and never write them: on a
  * plan with gains they return MCS_E_UNSUPPORTED (apply mcs_gain_apply_device to the frames and
- * stitch with a plan without gains).  Host-side only; keeps the prepared tables.  A gain that is
- * not finite and positive: MCS_E_INVALID. */
+ * stitch with a plan without gains) -- or call mcs_stitch_device_gained /
+ * mcs_stitch_direct_gained below, which apply the gains inside the stitch kernels.  Host-side
+ * only; keeps the prepared tables.  A gain that is not finite and positive: MCS_E_INVALID. */
 int mcs_plan_set_gains(mcs_plan *plan, const double *gains);
+/* mcs_stitch_device / mcs_stitch_direct with the plan's gains fused into the kernels: the same
+ * arguments and checks; every tap byte goes through p' = min(255, (p q + 128) >> 8) on its way
+ * from the frame to the bilinear weights, so the mosaic equals the stitch of the pre-gained
+ * frames bit for bit, in every blend mode, while the caller's frames are only read and no copy of
+ * them is made.  The gains are the plan's q at the time of the call (they travel by value in the
+ * kernel arguments): a launch in flight keeps them when mcs_plan_set_gains changes the plan.  On
+ * a plan with gains disabled, or with q = 256 for every camera the mosaic uses, the calls launch
+ * exactly what their ungained twins launch.  mcs_stitch_device_gained on a multi-band plan whose
+ * tables were prepared for the opt-in sweep (MCS_MB_SWEEP=1) with gains other than the identity:
+ * MCS_E_UNSUPPORTED (the sweep kernel has no gained variant). */
+int mcs_stitch_device_gained(mcs_plan *plan, const uint8_t *const *d_cams,
+                             const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                             int64_t out_frame_stride, int n_frames, void *stream);
+int mcs_stitch_direct_gained(mcs_plan *plan, const uint8_t *const *d_cams,
+                             const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                             int64_t out_frame_stride, int n_frames, void *stream);
 /* q[i] of every camera (256 when gains are disabled) and whether gains are enabled; either
  * pointer may be NULL. */
 int mcs_plan_gains(const mcs_plan *plan, uint16_t *q, int *enabled);

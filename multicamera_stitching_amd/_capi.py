@@ -53,7 +53,7 @@ EXPORTS = (
     "mcs_rig_job_wait_stitch", "mcs_rig_job_create_batch", "mcs_rig_job_wait_stitch_batch",
     "mcs_plan_set_lens", "mcs_lens_map_host", "mcs_plan_overlap_stats",
     "mcs_plan_overlap_stats_host", "mcs_gain_solve_host", "mcs_plan_set_gains", "mcs_plan_gains",
-    "mcs_gain_apply_device",
+    "mcs_gain_apply_device", "mcs_stitch_device_gained", "mcs_stitch_direct_gained",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -274,6 +274,10 @@ def load() -> ctypes.CDLL:
         L.mcs_stitch_device.restype = I
         L.mcs_stitch_direct.argtypes = L.mcs_stitch_device.argtypes
         L.mcs_stitch_direct.restype = I
+        L.mcs_stitch_device_gained.argtypes = L.mcs_stitch_device.argtypes
+        L.mcs_stitch_device_gained.restype = I
+        L.mcs_stitch_direct_gained.argtypes = L.mcs_stitch_device.argtypes
+        L.mcs_stitch_direct_gained.restype = I
         L.mcs_group_unique_id.argtypes = [P]
         L.mcs_group_unique_id.restype = I
         L.mcs_group_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]
@@ -520,6 +524,28 @@ class Plan:
         check(self._lib.mcs_stitch_direct(self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)),
                                           int(out_pitch), int(out_frame_stride), int(n_frames),
                                           ctypes.c_void_p(int(stream))))
+
+    def stitch_device_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
+                             out_frame_stride: int, n_frames: int, stream: int = 0):
+        """mcs_stitch_device_gained: stitch_device with the plan's gains (set_gains) applied
+        inside the kernels -- the frames are only read; the mosaic is that of the pre-gained
+        frames, bit for bit."""
+        n = len(cam_ptrs)
+        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
+        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
+        check(self._lib.mcs_stitch_device_gained(
+            self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
+            int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(stream))))
+
+    def stitch_direct_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
+                             out_frame_stride: int, n_frames: int, stream: int = 0):
+        """mcs_stitch_direct_gained: stitch_direct with the plan's gains inside the kernel."""
+        n = len(cam_ptrs)
+        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
+        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
+        check(self._lib.mcs_stitch_direct_gained(
+            self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
+            int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(stream))))
 
     def prepare(self, stream: int = 0):
         """Evaluate and store the plan's map tables on its device (once)."""

@@ -85,10 +85,11 @@ __device__ __forceinline__ int blend_owner(const KParams &P, int x, int y, uint3
 }
 
 // Bilinear sample at (x32, y32) with the taps clamped into the image (BORDER_REPLICATE), the
-// remapBilinear fixed point; channel k in byte k.  One 8-byte window load per tap row.
-template <int CN>
+// remapBilinear fixed point; channel k in byte k.  One 8-byte window load per tap row.  GAIN (the
+// _g feather kernel): gain q on every tap byte first (gain_byte).
+template <int CN, bool GAIN = false>
 __device__ __forceinline__ uint32_t sample_replicate(const uint8_t *fb, int w, int h, int x32,
-                                                     int y32)
+                                                     int y32, uint32_t q = 256u)
 {
     const int sx = x32 >> 5, sy = y32 >> 5, fx = x32 & 31, fy = y32 & 31;
     const int cx = w >= 2 ? min(max(sx, 0), w - 2) : 0;
@@ -102,8 +103,13 @@ __device__ __forceinline__ uint32_t sample_replicate(const uint8_t *fb, int w, i
     uint32_t r = 0;
 #pragma unroll
     for (int k = 0; k < CN; k++) {
-        const int s = (int)byte_of(r0, oa + k) * w00 + (int)byte_of(r0, ob + k) * w01 +
-                      (int)byte_of(r1, oa + k) * w10 + (int)byte_of(r1, ob + k) * w11;
+        uint32_t p00 = byte_of(r0, oa + k), p01 = byte_of(r0, ob + k);
+        uint32_t p10 = byte_of(r1, oa + k), p11 = byte_of(r1, ob + k);
+        if constexpr (GAIN) {
+            p00 = gain_byte(p00, q), p01 = gain_byte(p01, q);
+            p10 = gain_byte(p10, q), p11 = gain_byte(p11, q);
+        }
+        const int s = (int)p00 * w00 + (int)p01 * w01 + (int)p10 * w10 + (int)p11 * w11;
         r |= (uint32_t)((s + 16384) >> 15) << (8 * k);
     }
     return r;
@@ -248,7 +254,7 @@ __device__ __forceinline__ void blend_classify(const KParams &P, int mode, const
 
 // ---- per frame ---------------------------------------------------------------------------------
 // Feather: grid (listed tiles, frames), block 256.
-template <int CN, int INTERP>
+template <int CN, int INTERP, bool GAIN = false>
 __device__ __forceinline__ void feather_tile(const KBlendArgs &a)
 {
     const KParams &P = a.P;
@@ -268,8 +274,9 @@ __device__ __forceinline__ void feather_tile(const KBlendArgs &a)
             slot_xy<INTERP>(P, s, x, y, x32, y32, cam, w, h);
             const int d = slot_dist(x32, y32, w, h);
             if (d <= 0) continue;
-            const uint32_t v = sample_replicate<CN>(P.cams[cam] + (int64_t)f * P.cam_fstride[cam],
-                                                    w, h, x32, y32);
+            const uint32_t v = sample_replicate<CN, GAIN>(
+                P.cams[cam] + (int64_t)f * P.cam_fstride[cam], w, h, x32, y32,
+                GAIN ? gain_q_of(P, cam) : 256u);
             den += d;
 #pragma unroll
             for (int k = 0; k < CN; k++) num[k] += d * (int)((v >> (8 * k)) & 0xffu);
@@ -486,16 +493,21 @@ __device__ __forceinline__ void mb_weights2(uint32_t meta, uint32_t &wa, uint32_
     wb = min((32u - fx) * yb, 65535u) | (min(fx * yb, 65535u) << 16);
 }
 
-// Channel k of a descriptor's sample from its two (shifted) row windows.
-template <int CN>
+// Channel k of a descriptor's sample from its two (shifted) row windows.  GAIN (the _g kernels):
+// the owner camera's gain g on the two tap bytes of each row first (gain_half).
+template <int CN, bool GAIN = false>
 __device__ __forceinline__ uint32_t mb_tap(uint2 r0, uint2 r1, uint32_t wa, uint32_t wb, int k,
-                                           uint32_t d)
+                                           uint32_t d, GainQ g = GainQ())
 {
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     const uint32_t sel = ((uint32_t)k | (0x0cu << 8) | ((uint32_t)(CN + k) << 16) | (0x0cu << 24)) +
                          d * 0x00010001u;
-    const uint32_t a0 = __builtin_amdgcn_perm(r0.y, r0.x, sel);
-    const uint32_t a1 = __builtin_amdgcn_perm(r1.y, r1.x, sel);
+    uint32_t a0 = __builtin_amdgcn_perm(r0.y, r0.x, sel);
+    uint32_t a1 = __builtin_amdgcn_perm(r1.y, r1.x, sel);
+    if constexpr (GAIN) {
+        a0 = gain_half(a0, g.h, g.l);
+        a1 = gain_half(a1, g.h, g.l);
+    }
     uint32_t v = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a0), __builtin_bit_cast(us2, wa),
                                         16384u, false);
     v = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a1), __builtin_bit_cast(us2, wb), v, false);
@@ -503,15 +515,19 @@ __device__ __forceinline__ uint32_t mb_tap(uint2 r0, uint2 r1, uint32_t wa, uint
 }
 
 // Channel k of a sample with mb_weights2's doubled weights: the value is byte 2 of the result.
-template <int CN>
+template <int CN, bool GAIN = false>
 __device__ __forceinline__ uint32_t mb_tap2(uint2 r0, uint2 r1, uint32_t wa, uint32_t wb, int k,
-                                            uint32_t d)
+                                            uint32_t d, GainQ g = GainQ())
 {
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     const uint32_t sel = ((uint32_t)k | (0x0cu << 8) | ((uint32_t)(CN + k) << 16) | (0x0cu << 24)) +
                          d * 0x00010001u;
-    const uint32_t a0 = __builtin_amdgcn_perm(r0.y, r0.x, sel);
-    const uint32_t a1 = __builtin_amdgcn_perm(r1.y, r1.x, sel);
+    uint32_t a0 = __builtin_amdgcn_perm(r0.y, r0.x, sel);
+    uint32_t a1 = __builtin_amdgcn_perm(r1.y, r1.x, sel);
+    if constexpr (GAIN) {
+        a0 = gain_half(a0, g.h, g.l);
+        a1 = gain_half(a1, g.h, g.l);
+    }
     const uint32_t v = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a0),
                                               __builtin_bit_cast(us2, wa), 32768u, false);
     return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a1), __builtin_bit_cast(us2, wb), v,
@@ -876,7 +892,7 @@ __device__ __forceinline__ int ch16(uint2 v, int k)
     return (int)((((k & 1) ? v.y : v.x) >> ((k & 2) ? 16 : 0)) & 0xffffu);
 }
 
-template <int CN>
+template <int CN, bool GAIN = false>
 __device__ __forceinline__ void mb_levels(const KMbArgs &a, MbLvLds<CN> &L)
 {
     constexpr int NT = kMbLvThreads, KJ = (kMbU + NT - 1) / NT;
@@ -897,6 +913,8 @@ __device__ __forceinline__ void mb_levels(const KMbArgs &a, MbLvLds<CN> &L)
     const unsigned d1m = (65536u + w1 - 1) / w1, d2m = (65536u + w2 - 1) / w2;   // / w1, / w2
     int cam, w, h;
     slot_info(P, mb_slot(mask, j), cam, w, h);
+    // (GAIN: the owner's camera is uniform over the block: its q halves live in SGPRs)
+    const GainQ gq = GAIN ? gain_pair(gain_q_of(P, cam)) : GainQ();
     const int64_t pitch = (int64_t)w * CN, fbytes = pitch * h;
     const MbFoot F = reinterpret_cast<const MbFoot *>(a.foot)[(int64_t)bt * a.slots + j];
     const bool staged = F.fits;                      // footprint through LDS (else global loads)
@@ -951,7 +969,7 @@ __device__ __forceinline__ void mb_levels(const KMbArgs &a, MbLvLds<CN> &L)
                 mb_weights(dmeta[kk], wa, wb);
                 px[kk] = 0;
 #pragma unroll
-                for (int k = 0; k < CN; k++) px[kk] |= mb_tap<CN>(r0, r1, wa, wb, k, 0u) << (8 * k);
+                for (int k = 0; k < CN; k++) px[kk] |= mb_tap<CN, GAIN>(r0, r1, wa, wb, k, 0u, gq) << (8 * k);
             }
 #pragma unroll
             for (int kk = 0; kk < KJ; kk++)
@@ -977,7 +995,7 @@ __device__ __forceinline__ void mb_levels(const KMbArgs &a, MbLvLds<CN> &L)
                 mb_weights(dmeta[kk], wa, wb);
                 px[kk] = 0;
 #pragma unroll
-                for (int k = 0; k < CN; k++) px[kk] |= mb_tap<CN>(r0, r1, wa, wb, k, d) << (8 * k);
+                for (int k = 0; k < CN; k++) px[kk] |= mb_tap<CN, GAIN>(r0, r1, wa, wb, k, d, gq) << (8 * k);
             }
 #pragma unroll
             for (int kk = 0; kk < KJ; kk++)
@@ -991,7 +1009,7 @@ __device__ __forceinline__ void mb_levels(const KMbArgs &a, MbLvLds<CN> &L)
                 uint32_t wa, wb, px = 0;
                 mb_weights((uint32_t)(v >> 32), wa, wb);
 #pragma unroll
-                for (int k = 0; k < CN; k++) px |= mb_tap<CN>(r0, r1, wa, wb, k, 0u) << (8 * k);
+                for (int k = 0; k < CN; k++) px |= mb_tap<CN, GAIN>(r0, r1, wa, wb, k, 0u, gq) << (8 * k);
                 L.g0[(uint32_t)(v >> 48) & 0x1fffu] = px;
             }
         }
@@ -1323,7 +1341,7 @@ constexpr int mb_lds_wait(int ph, bool first)
 // too (16 B per lane and row: windows, meta, the offset of the group issued after that row), so
 // the loop holds no ordinary global load: the compiler's own vmcnt waits for ordinary loads
 // would otherwise drain the LDS-DMAs every row.
-template <int CN, int FR, bool BR, int WM>
+template <int CN, int FR, bool BR, int WM, bool GAIN = false>
 __device__ __forceinline__ void mb_bands_body(const KMbBandArgs &a, int bi, lds_u8 *ring, int pr)
 {
     constexpr bool AL = WM >= 1, LD = WM == 2;
@@ -1345,6 +1363,10 @@ __device__ __forceinline__ void mb_bands_body(const KMbBandArgs &a, int bi, lds_
     if (fl0 >= a.nf) return;
     int cam, w, h;
     slot_info(P, B.slot, cam, w, h);
+    // (GAIN: the band's owner camera is uniform over the wave: its q halves live in SGPRs; the
+    // gain is VALU between the window reads and the udot2 -- no memory operation, so the counted
+    // waits of the LDS-ring form hold as they are)
+    const GainQ gq = GAIN ? gain_pair(gain_q_of(P, cam)) : GainQ();
     const uint32_t pitch = (uint32_t)(w * CN);
     const gu8 *fb[FR];
 #pragma unroll
@@ -1671,7 +1693,7 @@ __device__ __forceinline__ void mb_bands_body(const KMbBandArgs &a, int bi, lds_
                 }
                 uint32_t t[4];
 #pragma unroll
-                for (int c = 0; c < 4; c++) t[c] = c < CN ? mb_tap2<CN>(r0, r1, wa, wb, c, dd) : 0u;
+                for (int c = 0; c < 4; c++) t[c] = c < CN ? mb_tap2<CN, GAIN>(r0, r1, wa, wb, c, dd, gq) : 0u;
                 if constexpr (CN >= 3) pls[f] = __builtin_amdgcn_perm(t[2], t[0], 0x0c060c02u);
                 else pls[f] = (t[0] >> 16) & 0xffu;
                 if constexpr (CN >= 4) phs[f] = __builtin_amdgcn_perm(t[3], t[1], 0x0c060c02u);
@@ -1729,15 +1751,15 @@ __device__ __forceinline__ void mb_bands_body(const KMbBandArgs &a, int bi, lds_
 
 // The band pass of band bi: the aligned launch (AL) runs bands flagged for the LDS ring (MbBand
 // pad_ bit 0, band_lds_tables) in mode 2, the others in mode 1.
-template <int CN, int FR, bool BR, bool AL>
+template <int CN, int FR, bool BR, bool AL, bool GAIN = false>
 __device__ __forceinline__ void mb_bands(const KMbBandArgs &a, int bi, lds_u8 *ring, int pr)
 {
     if constexpr (AL) {
         const int lds = __builtin_amdgcn_readfirstlane(a.bands[bi].pad_) & 1;
-        if (lds) mb_bands_body<CN, FR, BR, 2>(a, bi, ring, pr);
-        else mb_bands_body<CN, FR, BR, 1>(a, bi, ring, pr);
+        if (lds) mb_bands_body<CN, FR, BR, 2, GAIN>(a, bi, ring, pr);
+        else mb_bands_body<CN, FR, BR, 1, GAIN>(a, bi, ring, pr);
     } else {
-        mb_bands_body<CN, FR, BR, 0>(a, bi, ring, pr);
+        mb_bands_body<CN, FR, BR, 0, GAIN>(a, bi, ring, pr);
     }
 }
 

@@ -476,9 +476,10 @@ int mcs_stitch_device(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *
 
 }  // extern "C"
 
-int mcs::stitch_device_frames(mcs_plan *p, const uint8_t *const *d_cams,
-                              const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                              int64_t out_frame_stride, int n_frames, void *stream)
+// mcs_stitch_device(_gained) after the refusals: the checks, the device, the launch.
+static int stitch_device_launch(mcs_plan *p, const uint8_t *const *d_cams,
+                                const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                                int64_t out_frame_stride, int n_frames, void *stream, bool gained)
 {
     mcs::KParams kp;
     int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
@@ -489,24 +490,33 @@ int mcs::stitch_device_frames(mcs_plan *p, const uint8_t *const *d_cams,
     DeviceGuard g(A, p->device);
     if (g.err != hipSuccess)
         return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
-    return launch_stitch(A, p, kp, n_frames, (hipStream_t)stream);
+    // (identity gains, or none: exactly the ungained launch)
+    return launch_stitch(A, p, kp, n_frames, (hipStream_t)stream, gained && gains_active(p));
 }
 
-extern "C" {
+int mcs::stitch_device_frames(mcs_plan *p, const uint8_t *const *d_cams,
+                              const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                              int64_t out_frame_stride, int n_frames, void *stream)
+{
+    return stitch_device_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                                n_frames, stream, false);
+}
 
-int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
-                      uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,
-                      void *stream)
+// mcs_stitch_direct(_gained) after the refusals.  gained: the _g kernels with the plan's q as of
+// this call in their arguments, unless every used camera's q is the identity.
+static int stitch_direct_launch(mcs_plan *p, const uint8_t *const *d_cams,
+                                const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                                int64_t out_frame_stride, int n_frames, void *stream, bool gained)
 {
     mcs::KParams kp;
-    int rc = refuse_gains(p, "mcs_stitch_direct");
-    if (rc) return rc;
-    rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride, n_frames,
-                        &kp);
+    int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                            n_frames, &kp);
     if (rc) return rc;
     if (p->blend != MCS_BLEND_NONE && p->blend != MCS_BLEND_SEAM)
         return mcs::fail(MCS_E_UNSUPPORTED, "mcs_stitch_direct renders paste / seam plans; "
                          "blended plans need their prepared tables (mcs_stitch_device)");
+    gained = gained && gains_active(p);
+    if (gained) fill_gain_q(p, &kp);
     if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames == 0) return MCS_OK;
     const Api *A = mcs::rt::api();
     if (!A) return MCS_E_HIP;
@@ -543,12 +553,43 @@ int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *
         args.n_frames = uniform ? n_frames : 1;
         args.pad_ = 0;
         const unsigned fy = (unsigned)((args.n_frames + mcs::kDirectFrames - 1) / mcs::kDirectFrames);
-        rc = launch_args(A, k->direct[p->fd.channels][p->fd.interp][off32 ? 1 : 0],
+        rc = launch_args(A, (gained ? k->direct_g : k->direct)[p->fd.channels][p->fd.interp]
+                                                               [off32 ? 1 : 0],
                          (unsigned)(gx * gy), fy, mcs::kWave, mcs::kWavesPerBlock, &args,
                          sizeof(args), s);
         if (rc) return rc;
     }
     return MCS_OK;
+}
+
+extern "C" {
+
+int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
+                      uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,
+                      void *stream)
+{
+    const int rc = refuse_gains(p, "mcs_stitch_direct");
+    if (rc) return rc;
+    return stitch_direct_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                                n_frames, stream, false);
+}
+
+// The fused forms: the plan's gains inside the kernels, on the taps (csrc/mcs_dev.h gain_half);
+// the caller's frames are only read.
+int mcs_stitch_device_gained(mcs_plan *p, const uint8_t *const *d_cams,
+                             const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                             int64_t out_frame_stride, int n_frames, void *stream)
+{
+    return stitch_device_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                                n_frames, stream, true);
+}
+
+int mcs_stitch_direct_gained(mcs_plan *p, const uint8_t *const *d_cams,
+                             const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
+                             int64_t out_frame_stride, int n_frames, void *stream)
+{
+    return stitch_direct_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                                n_frames, stream, true);
 }
 
 int mcs_plan_prepare(mcs_plan *p, void *stream)

@@ -267,6 +267,50 @@ __device__ __forceinline__ uint2 lds_window(const uint8_t *smem, uint32_t a)
     return r;
 }
 
+// Exposure gain on source bytes (include/mcs.h "Exposure"; mcs_gain_apply and the fused _g
+// kernels share this arithmetic).
+// (p q + 128) >> 8 of the four bytes of a word, saturated to 255, in packed 16-bit lanes: with
+// q = 256 qh + ql, (p q + 128) >> 8 = p qh + ((p ql + 128) >> 8), and every term and the sum fit
+// 16 bits (255 * 255 + 254 < 65536).
+typedef unsigned short gain_us2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t gain_half(uint32_t even, gain_us2 qh, gain_us2 ql)
+{
+    const gain_us2 p = __builtin_bit_cast(gain_us2, even);
+    const gain_us2 c128 = {128, 128}, c255 = {255, 255};
+    gain_us2 r = p * qh + ((p * ql + c128) >> 8);
+    r = __builtin_elementwise_min(r, c255);
+    return __builtin_bit_cast(uint32_t, r);
+}
+__device__ __forceinline__ uint32_t gain_word(uint32_t w, gain_us2 qh, gain_us2 ql)
+{
+    return gain_half(w & 0x00ff00ffu, qh, ql) | (gain_half((w >> 8) & 0x00ff00ffu, qh, ql) << 8);
+}
+__device__ __forceinline__ uint8_t gain_byte(uint32_t p, uint32_t q)
+{
+    return (uint8_t)min(255u, (p * q + 128u) >> 8);
+}
+
+// The packed halves of a gain q = 256 qh + ql, as gain_half takes them.
+struct GainQ {
+    gain_us2 h, l;
+};
+__device__ __forceinline__ GainQ gain_pair(uint32_t q)
+{
+    GainQ g;
+    g.h = gain_us2{(unsigned short)(q >> 8), (unsigned short)(q >> 8)};
+    g.l = gain_us2{(unsigned short)(q & 255u), (unsigned short)(q & 255u)};
+    return g;
+}
+
+// q of camera `cam` at this launch (KParams::gain_q), read as the dword that holds it from the
+// constant address space: a scalar load for a wave-uniform camera, a vector load otherwise.
+__device__ __forceinline__ uint32_t gain_q_of(const KParams &P, int cam)
+{
+    typedef __attribute__((address_space(4))) const uint32_t cu32;
+    const uint32_t w = ((const cu32 *)P.gain_q)[cam >> 1];
+    return (cam & 1) ? w >> 16 : w & 0xffffu;
+}
+
 // Bilinear weights of the stitch kernels as u16 pairs: remapBilinear's 15-bit weight w (the four
 // sum to 32768) is stored doubled, min(2 w, 65535), so that a channel's sum
 // s = sum p (2 w) + 32768 carries (sum p w + 2^14) >> 15 -- remapBilinear's value -- in its
@@ -276,13 +320,20 @@ __device__ __forceinline__ uint32_t w2x(uint32_t w) { return w >= 32768u ? 65535
 
 // Channel k of a pixel from its two row windows (v_perm_b32 + 2 x v_dot2_u32_u16): the result
 // byte is byte 2 of the returned sum (bits 24+ are 0).
-template <int CN>
-__device__ __forceinline__ uint32_t blend(uint2 r0, uint2 r1, uint32_t w0, uint32_t w1, int k)
+// GAIN (the _g kernels): the pixel's camera gain g on the tap bytes, a u16 pair per row, before
+// the weights (gain_half: every tap byte goes through the rounding and the clamp).
+template <int CN, bool GAIN = false>
+__device__ __forceinline__ uint32_t blend(uint2 r0, uint2 r1, uint32_t w0, uint32_t w1, int k,
+                                          GainQ g = GainQ())
 {
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     const uint32_t sel = (uint32_t)k | (0x0cu << 8) | ((uint32_t)(CN + k) << 16) | (0x0cu << 24);
-    const uint32_t a0 = __builtin_amdgcn_perm(r0.y, r0.x, sel);
-    const uint32_t a1 = __builtin_amdgcn_perm(r1.y, r1.x, sel);
+    uint32_t a0 = __builtin_amdgcn_perm(r0.y, r0.x, sel);
+    uint32_t a1 = __builtin_amdgcn_perm(r1.y, r1.x, sel);
+    if constexpr (GAIN) {
+        a0 = gain_half(a0, g.h, g.l);
+        a1 = gain_half(a1, g.h, g.l);
+    }
     uint32_t s = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a0), __builtin_bit_cast(us2, w0),
                                         32768u, false);
     s = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a1), __builtin_bit_cast(us2, w1), s, false);

@@ -142,28 +142,7 @@ __device__ __forceinline__ void overlap_sum(const KOverlapSumArgs &a)
     atomicAdd(&a.S[((int64_t)(f0 + f) * a.n_cams + i) * a.n_cams + j], (unsigned long long)s);
 }
 
-// ---- gain on source bytes ---------------------------------------------------------------------
-// (p q + 128) >> 8 of the four bytes of a word, saturated to 255, in packed 16-bit lanes: with
-// q = 256 qh + ql, (p q + 128) >> 8 = p qh + ((p ql + 128) >> 8), and every term and the sum fit
-// 16 bits (255 * 255 + 254 < 65536).
-typedef unsigned short gain_us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t gain_half(uint32_t even, gain_us2 qh, gain_us2 ql)
-{
-    const gain_us2 p = __builtin_bit_cast(gain_us2, even);
-    const gain_us2 c128 = {128, 128}, c255 = {255, 255};
-    gain_us2 r = p * qh + ((p * ql + c128) >> 8);
-    r = __builtin_elementwise_min(r, c255);
-    return __builtin_bit_cast(uint32_t, r);
-}
-__device__ __forceinline__ uint32_t gain_word(uint32_t w, gain_us2 qh, gain_us2 ql)
-{
-    return gain_half(w & 0x00ff00ffu, qh, ql) | (gain_half((w >> 8) & 0x00ff00ffu, qh, ql) << 8);
-}
-__device__ __forceinline__ uint8_t gain_byte(uint32_t p, uint32_t q)
-{
-    return (uint8_t)min(255u, (p * q + 128u) >> 8);
-}
-
+// ---- gain on source bytes (gain_half, gain_word, gain_byte: mcs_dev.h) -----------------------
 // grid (ceil(bytes / kGainChunk) + 1, frames), block kGainThreads.  Per frame the destination's
 // 16-byte aligned body moves as 16-byte vectors (the source side of an out-of-place call may be
 // unaligned: an unaligned dwordx4 load), its head and tail as bytes by the last block of the row.

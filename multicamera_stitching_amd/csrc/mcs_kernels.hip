@@ -230,9 +230,10 @@ __device__ __forceinline__ Geo describe_geo(const KParams &P, int x, int y)
 
 // Global-gather form of a pixel (tiles whose footprint does not fit the LDS budget).
 template <int CN, int INTERP, bool OFF32>
-__device__ __forceinline__ Desc<OFF32> describe(const KParams &P, int x, int y)
+__device__ __forceinline__ Desc<OFF32> describe(const KParams &P, int x, int y, int *cam = nullptr)
 {
     const Geo g = describe_geo<CN, INTERP>(P, x, y);
+    if (cam) *cam = g.cam;   // (the _g kernels: whose gain the pixel takes)
     Desc<OFF32> d;
     const int64_t pitch = (int64_t)g.cw * CN, fbytes = pitch * g.ch;
     const int64_t o0 = (int64_t)g.r0 * pitch + g.c0, o1 = (int64_t)g.r1 * pitch + g.c1;
@@ -259,16 +260,20 @@ __device__ __forceinline__ uint2 shr_bytes(uint2 v, uint32_t n)
 
 // Direct global-gather path for the 4 pixels at (xg, y): descriptors once, then every capture
 // (frame stride P.cam_fstride[0] for all cameras; the host splits batches that differ).
-template <int CN, int INTERP, bool OFF32>
+// GAIN: each pixel's taps take its camera's gain (KParams::gain_q), looked up once per launch.
+template <int CN, int INTERP, bool OFF32, bool GAIN = false>
 __device__ __forceinline__ void stitch_direct(const KParams &P, int f0, int n_frames, int xg,
                                               int y)
 {
     const int npx = min(kPx, P.out_w - xg);
     Desc<OFF32> d[kPx];
+    uint32_t qv[kPx];   // (GAIN) q of each pixel's camera
     uint32_t any_shift = 0;
 #pragma unroll
     for (int p = 0; p < kPx; p++) {
-        d[p] = describe<CN, INTERP, OFF32>(P, min(xg + p, P.out_w - 1), y);
+        int cam = 0;
+        d[p] = describe<CN, INTERP, OFF32>(P, min(xg + p, P.out_w - 1), y, GAIN ? &cam : nullptr);
+        qv[p] = GAIN ? gain_q_of(P, cam) : 0u;
         any_shift |= d[p].shift;
     }
     const int64_t fstride = P.cam_fstride[0];
@@ -291,9 +296,12 @@ __device__ __forceinline__ void stitch_direct(const KParams &P, int f0, int n_fr
         }
         uint32_t rr[kPx * CN];
 #pragma unroll
-        for (int p = 0; p < kPx; p++)
+        for (int p = 0; p < kPx; p++) {
+            const GainQ gq = GAIN ? gain_pair(qv[p]) : GainQ();
 #pragma unroll
-            for (int k = 0; k < CN; k++) rr[p * CN + k] = blend<CN>(r0[p], r1[p], d[p].w0, d[p].w1, k);
+            for (int k = 0; k < CN; k++)
+                rr[p * CN + k] = blend<CN, GAIN>(r0[p], r1[p], d[p].w0, d[p].w1, k, gq);
+        }
         const OutWords w = pack_words<CN>(rr);
         uint8_t *o = dst + (int64_t)f * P.out_fstride;
         if (wide) {
@@ -653,7 +661,7 @@ __device__ __forceinline__ void wait_vmcnt_jump(uint32_t entry)
 // walked in list (row-major) order; vertically adjacent tiles, whose footprints overlap
 // by a few source rows, then run at about the same time on the same L2.  (Placement affects
 // speed only.)
-template <int CN, bool BUF, int FITS = 1>
+template <int CN, bool BUF, int FITS = 1, bool GAIN = false>
 __device__ __forceinline__ void stream_tile(const KParams &P, const TileHdr *tiles,
                                             const uint32_t *desc, const uint32_t *desc4,
                                             const uint16_t *spans, int n_frames, int parts,
@@ -729,6 +737,28 @@ __device__ __forceinline__ void stream_tile(const KParams &P, const TileHdr *til
             d[p * kDescWords + 2] = d2;
         }
     }
+    // GAIN: the q of the tile's (at most kTileCams) cameras, fetched once per tile; a pixel's
+    // camera is the footprint slot its row-0 window lies in (TileHdr::base ascends over the live
+    // slots; both descriptor forms carry the window address, and a pixel without a live tap has
+    // weights 0, whatever its q).  One q per pixel stays in a register, its halves are derived
+    // per capture.
+    uint32_t qv[kPx];
+#pragma unroll
+    for (int p = 0; p < kPx; p++) qv[p] = 0u;
+    if constexpr (GAIN) {
+        const int ncam = uni(h.ncam);
+        uint32_t tq[kTileCams];
+#pragma unroll
+        for (int k = 0; k < kTileCams; k++) tq[k] = gain_q_of(P, uni(h.cam[k]));
+#pragma unroll
+        for (int p = 0; p < kPx; p++) {
+            const int a0 = (int)(d[p * kDescWords] & 0xffffu);
+            uint32_t q = tq[0];
+#pragma unroll
+            for (int k = 1; k < kTileCams; k++) q = (k < ncam && a0 >= uni(h.base[k])) ? tq[k] : q;
+            qv[p] = q;
+        }
+    }
     const WaveWins<BUF, NJ> J =
         wave_windows<CN, BUF, NJ>(P, h, wave, spans + (int64_t)tile * kMaxTileJobs, lane);
 #define MCS_STAGE(slot, foff) stage_windows<BUF, NJ>(J, rs, (slot) - sizeof(TileHdr), (foff))
@@ -772,9 +802,11 @@ __device__ __forceinline__ void stream_tile(const KParams &P, const TileHdr *til
                                         __builtin_amdgcn_alignbyte(raw[p][2], raw[p][1], s0));
             const uint2 r1 = make_uint2(__builtin_amdgcn_alignbyte(raw[p][4], raw[p][3], s1),
                                         __builtin_amdgcn_alignbyte(raw[p][5], raw[p][4], s1));
+            const GainQ gq = GAIN ? gain_pair(qv[p]) : GainQ();
 #pragma unroll
             for (int k = 0; k < CN; k++)
-                rr[p * CN + k] = blend<CN>(r0, r1, d[p * kDescWords + 1], d[p * kDescWords + 2], k);
+                rr[p * CN + k] = blend<CN, GAIN>(r0, r1, d[p * kDescWords + 1],
+                                                 d[p * kDescWords + 2], k, gq);
         }
         const OutWords w = pack_words<CN>(rr);
         uint32_t *o32 = reinterpret_cast<uint32_t *>(dst + of);
@@ -830,7 +862,7 @@ __device__ __forceinline__ void stream_tile(const KParams &P, const TileHdr *til
 // Direct global gather for the tiles prepare could not fit in LDS (list in fallback[1..]):
 // grid (tiles, ceil(frames / kDirectFrames)), launched on a side stream next to the streaming
 // kernel, so these few tiles cost no extra time on the critical path.
-template <int CN, int INTERP, bool OFF32>
+template <int CN, int INTERP, bool OFF32, bool GAIN = false>
 __device__ __forceinline__ void direct_tile(const KParams &P, const int *fallback, int n_frames)
 {
     const int tile = fallback ? fallback[1 + blockIdx.x] : (int)blockIdx.x;   // NULL: every tile
@@ -840,7 +872,7 @@ __device__ __forceinline__ void direct_tile(const KParams &P, const int *fallbac
     int xg, y;
     tile_pixel(tx, ty, threadIdx.x, threadIdx.y, xg, y);
     if (xg < P.out_w && y < P.out_h && !(P.skip && P.skip[(int64_t)y * P.out_w + xg]))
-        stitch_direct<CN, INTERP, OFF32>(P, f0, min(n_frames, f0 + kDirectFrames), xg, y);
+        stitch_direct<CN, INTERP, OFF32, GAIN>(P, f0, min(n_frames, f0 + kDirectFrames), xg, y);
 }
 
 // Footprint marking: mask[cam][pixel] = 1 for every source pixel the mosaic reads with a
@@ -964,40 +996,50 @@ __device__ __forceinline__ void resize_px(const KResizeArgs &a)
     {                                                                                          \
         mcs::prepare_tile<CN, IN>(P, tiles, desc, desc4, fallback, big, spans);                \
     }
-#define MCS_STREAM_ENTRY(CN, SUF, BUF)                                                         \
-    extern "C" __global__ __launch_bounds__(512) void mcs_stream_c##CN##SUF(         \
-        const mcs::KParams P, const mcs::TileHdr *tiles, const uint32_t *desc,                \
-        const uint32_t *desc4, const uint16_t *spans, int n_frames, int parts,                \
+// (GS / GAIN: the fused-gain twins, suffix _g -- the same code with the camera gains on the taps)
+#define MCS_STREAM_ENTRY(CN, SUF, BUF, GS, GAIN)                                               \
+    extern "C" __global__ __launch_bounds__(512) void mcs_stream_c##CN##SUF##GS(               \
+        const mcs::KParams P, const mcs::TileHdr *tiles, const uint32_t *desc,                 \
+        const uint32_t *desc4, const uint16_t *spans, int n_frames, int parts,                 \
         const int *order, int n_order)                                                         \
     {                                                                                          \
         extern __shared__ __attribute__((aligned(16))) uint8_t smem[];                         \
-        mcs::stream_tile<CN, BUF>(P, tiles, desc, desc4, spans, n_frames, parts, order,        \
-                                  n_order, smem);                                              \
+        mcs::stream_tile<CN, BUF, 1, GAIN>(P, tiles, desc, desc4, spans, n_frames, parts,      \
+                                           order, n_order, smem);                              \
     }                                                                                          \
-    extern "C" __global__ __launch_bounds__(512) void mcs_stream_big_c##CN##SUF(               \
-        const mcs::KParams P, const mcs::TileHdr *tiles, const uint32_t *desc,                \
-        const uint32_t *desc4, const uint16_t *spans, int n_frames, int parts,                \
+    extern "C" __global__ __launch_bounds__(512) void mcs_stream_big_c##CN##SUF##GS(           \
+        const mcs::KParams P, const mcs::TileHdr *tiles, const uint32_t *desc,                 \
+        const uint32_t *desc4, const uint16_t *spans, int n_frames, int parts,                 \
         const int *order, int n_order)                                                         \
     {                                                                                          \
         extern __shared__ __attribute__((aligned(16))) uint8_t smem[];                         \
-        mcs::stream_tile<CN, BUF, 2>(P, tiles, desc, desc4, spans, n_frames, parts, order,     \
-                                     n_order, smem);                                           \
+        mcs::stream_tile<CN, BUF, 2, GAIN>(P, tiles, desc, desc4, spans, n_frames, parts,      \
+                                           order, n_order, smem);                              \
     }
-#define MCS_DIRECT_ENTRY(CN, IN, O32)                                                          \
-    extern "C" __global__ __launch_bounds__(512) void mcs_direct_c##CN##_i##IN##_o##O32(       \
-        const mcs::KParams P, const int *fallback, int n_frames)                              \
+#define MCS_DIRECT_ENTRY(CN, IN, O32, GS, GAIN)                                                \
+    extern "C" __global__ __launch_bounds__(512) void mcs_direct_c##CN##_i##IN##_o##O32##GS(   \
+        const mcs::KParams P, const int *fallback, int n_frames)                               \
     {                                                                                          \
-        mcs::direct_tile<CN, IN, O32 == 32>(P, fallback, n_frames);                            \
+        mcs::direct_tile<CN, IN, O32 == 32, GAIN>(P, fallback, n_frames);                      \
     }
 #define MCS_ENTRIES(CN)                                                                        \
     MCS_PREPARE_ENTRY(CN, 0)                                                                   \
     MCS_PREPARE_ENTRY(CN, 1)                                                                   \
-    MCS_STREAM_ENTRY(CN, , false)                                                              \
-    MCS_STREAM_ENTRY(CN, _b32, true)                                                           \
-    MCS_DIRECT_ENTRY(CN, 0, 32)                                                                \
-    MCS_DIRECT_ENTRY(CN, 1, 32)                                                                \
-    MCS_DIRECT_ENTRY(CN, 0, 64)                                                                \
-    MCS_DIRECT_ENTRY(CN, 1, 64)
+    MCS_STREAM_ENTRY(CN, , false, , false)                                                     \
+    MCS_STREAM_ENTRY(CN, _b32, true, , false)                                                  \
+    MCS_DIRECT_ENTRY(CN, 0, 32, , false)                                                       \
+    MCS_DIRECT_ENTRY(CN, 1, 32, , false)                                                       \
+    MCS_DIRECT_ENTRY(CN, 0, 64, , false)                                                       \
+    MCS_DIRECT_ENTRY(CN, 1, 64, , false)
+// (the _g twins are defined after every other kernel, at the end of this file: the kernels that
+// were there before them keep their order and their place in the code object)
+#define MCS_ENTRIES_G(CN)                                                                      \
+    MCS_STREAM_ENTRY(CN, , false, _g, true)                                                    \
+    MCS_STREAM_ENTRY(CN, _b32, true, _g, true)                                                 \
+    MCS_DIRECT_ENTRY(CN, 0, 32, _g, true)                                                      \
+    MCS_DIRECT_ENTRY(CN, 1, 32, _g, true)                                                      \
+    MCS_DIRECT_ENTRY(CN, 0, 64, _g, true)                                                      \
+    MCS_DIRECT_ENTRY(CN, 1, 64, _g, true)
 MCS_ENTRIES(1)
 MCS_ENTRIES(2)
 MCS_ENTRIES(3)
@@ -1006,7 +1048,7 @@ MCS_ENTRIES(4)
 // Blended modes (mcs_blend.h).  Prepare: owner map + tile info over the 32-px blend grid, then
 // the classification into the per-frame tile list; per frame: feather / multiband over it.
 #define MCS_BLEND_PREP_ENTRY(IN)                                                               \
-    extern "C" __global__ __launch_bounds__(256) void mcs_blend_owner_i##IN(                  \
+    extern "C" __global__ __launch_bounds__(256) void mcs_blend_owner_i##IN(                   \
         const mcs::KBlendPrepArgs a)                                                           \
     {                                                                                          \
         mcs::blend_owner_tile<IN>(a.P, a.owner, a.info);                                       \
@@ -1031,12 +1073,14 @@ extern "C" __global__ __launch_bounds__(256) void mcs_blend_classify(const mcs::
 {
     mcs::blend_classify(a.P, a.mode, a.owner, a.info, a.list, a.overflow, a.list2);
 }
-#define MCS_BLEND_ENTRY(CN, IN)                                                                \
-    extern "C" __global__ __launch_bounds__(256) void mcs_feather_c##CN##_i##IN(               \
+#define MCS_FEATHER_ENTRY(CN, IN, GS, GAIN)                                                    \
+    extern "C" __global__ __launch_bounds__(256) void mcs_feather_c##CN##_i##IN##GS(           \
         const mcs::KBlendArgs a)                                                               \
     {                                                                                          \
-        mcs::feather_tile<CN, IN>(a);                                                          \
-    }                                                                                          \
+        mcs::feather_tile<CN, IN, GAIN>(a);                                                    \
+    }
+#define MCS_BLEND_ENTRY(CN, IN)                                                                \
+    MCS_FEATHER_ENTRY(CN, IN, , false)                                                         \
     extern "C" __global__ __launch_bounds__(256) void mcs_mb_prep_c##CN##_i##IN(               \
         const mcs::KMbArgs a)                                                                  \
     {                                                                                          \
@@ -1063,29 +1107,29 @@ extern "C" __global__ __launch_bounds__(256) void mcs_blend_classify(const mcs::
 #define MCS_MB_BAND_RING(AL)                                                                   \
     __shared__ __attribute__((aligned(16))) uint8_t ring_[(AL) ? mcs::kMbLdsBytes : 16];       \
     mcs::lds_u8 *const ring = (mcs::lds_u8 *)ring_
-#define MCS_MB_BANDS_ENTRY(CN, SFX, AL)                                                        \
-    extern "C" __global__ __launch_bounds__(64) MCS_MB_BAND_ATTR(CN) void                     \
-        mcs_mb_bands##SFX##_c##CN(                                                             \
+#define MCS_MB_BANDS_ENTRY(CN, SFX, AL, GS, GAIN)                                              \
+    extern "C" __global__ __launch_bounds__(64) MCS_MB_BAND_ATTR(CN) void                      \
+        mcs_mb_bands##SFX##_c##CN##GS(                                                         \
         const mcs::KMbBandArgs a)                                                              \
     {                                                                                          \
         MCS_MB_BAND_RING(AL);                                                                  \
         int bl, pr;                                                                            \
         if (!mcs::xcd_unit(a.nb, (a.nf + mcs::kMbBandFrames - 1) / mcs::kMbBandFrames, bl, pr)) \
             return;                                                                            \
-        mcs::mb_bands<CN, mcs::kMbBandFrames, false, AL>(a, a.band0 + bl, ring, pr);          \
+        mcs::mb_bands<CN, mcs::kMbBandFrames, false, AL, GAIN>(a, a.band0 + bl, ring, pr);     \
     }                                                                                          \
-    extern "C" __global__ __launch_bounds__(64) MCS_MB_BAND_ATTR(CN) void                     \
-        mcs_mb_bands_br##SFX##_c##CN(                                                          \
+    extern "C" __global__ __launch_bounds__(64) MCS_MB_BAND_ATTR(CN) void                      \
+        mcs_mb_bands_br##SFX##_c##CN##GS(                                                      \
         const mcs::KMbBandArgs a)                                                              \
     {                                                                                          \
         MCS_MB_BAND_RING(AL);                                                                  \
         int bl, pr;                                                                            \
         if (!mcs::xcd_unit(a.nb, (a.nf + mcs::kMbBandFrames - 1) / mcs::kMbBandFrames, bl, pr)) \
             return;                                                                            \
-        mcs::mb_bands<CN, mcs::kMbBandFrames, true, AL>(a, a.band0 + bl, ring, pr);           \
+        mcs::mb_bands<CN, mcs::kMbBandFrames, true, AL, GAIN>(a, a.band0 + bl, ring, pr);      \
     }                                                                                          \
-    extern "C" __global__ __launch_bounds__(64) MCS_MB_BAND_ATTR(CN) void                     \
-        mcs_mb_bands_all##SFX##_c##CN(                                                         \
+    extern "C" __global__ __launch_bounds__(64) MCS_MB_BAND_ATTR(CN) void                      \
+        mcs_mb_bands_all##SFX##_c##CN##GS(                                                     \
         const mcs::KMbBandArgs a)                                                              \
     {                                                                                          \
         MCS_MB_BAND_RING(AL);                                                                  \
@@ -1093,18 +1137,28 @@ extern "C" __global__ __launch_bounds__(256) void mcs_blend_classify(const mcs::
         if (!mcs::xcd_unit(a.nb, (a.nf + mcs::kMbBandFrames - 1) / mcs::kMbBandFrames, bl, pr)) \
             return;                                                                            \
         if (bl < a.n_in)                                                                       \
-            mcs::mb_bands<CN, mcs::kMbBandFrames, false, AL>(a, a.band0 + bl, ring, pr);      \
-        else mcs::mb_bands<CN, mcs::kMbBandFrames, true, AL>(a, a.band1 + bl - a.n_in, ring, pr); \
+            mcs::mb_bands<CN, mcs::kMbBandFrames, false, AL, GAIN>(a, a.band0 + bl, ring, pr); \
+        else                                                                                   \
+            mcs::mb_bands<CN, mcs::kMbBandFrames, true, AL, GAIN>(a, a.band1 + bl - a.n_in,    \
+                                                                  ring, pr);                   \
     }
-#define MCS_MB_ENTRY(CN)                                                                       \
+#define MCS_MB_LEVELS_ENTRY(CN, GS, GAIN)                                                      \
     extern "C" __global__ __launch_bounds__(MCS_MB_LV_THREADS) __attribute__((amdgpu_waves_per_eu(MCS_MB_WAVES))) \
-    void mcs_mb_levels_c##CN(const mcs::KMbArgs a)                                             \
+    void mcs_mb_levels_c##CN##GS(const mcs::KMbArgs a)                                         \
     {                                                                                          \
         __shared__ mcs::MbLvLds<CN> lds;                                                       \
-        mcs::mb_levels<CN>(a, lds);                                                            \
-    }                                                                                          \
-    MCS_MB_BANDS_ENTRY(CN, , false)                                                            \
-    MCS_MB_BANDS_ENTRY(CN, _a, true)                                                           \
+        mcs::mb_levels<CN, GAIN>(a, lds);                                                      \
+    }
+// (the blend kernels read no source byte -- level 0 of the owner is the owner sample already in
+// the mosaic, the levels come from the scratch -- so they have no _g twin)
+#define MCS_MB_ENTRY_G(CN)                                                                     \
+    MCS_MB_LEVELS_ENTRY(CN, _g, true)                                                          \
+    MCS_MB_BANDS_ENTRY(CN, , false, _g, true)                                                  \
+    MCS_MB_BANDS_ENTRY(CN, _a, true, _g, true)
+#define MCS_MB_ENTRY(CN)                                                                       \
+    MCS_MB_LEVELS_ENTRY(CN, , false)                                                           \
+    MCS_MB_BANDS_ENTRY(CN, , false, , false)                                                   \
+    MCS_MB_BANDS_ENTRY(CN, _a, true, , false)                                                  \
     extern "C" __global__ __launch_bounds__(MCS_MB_BL_THREADS) void                            \
         mcs_mb_blend_c##CN##_s2(                                                               \
         const mcs::KMbArgs a)                                                                  \
@@ -1188,3 +1242,22 @@ extern "C" __global__ __launch_bounds__(256) void mcs_gain_apply(const mcs::KGai
 {
     mcs::gain_apply(a);
 }
+
+// The fused-gain twins (suffix _g; DESIGN section 5 "Exposure"): every kernel that reads source
+// bytes per launch, with the camera gains of KParams::gain_q on its taps.
+MCS_ENTRIES_G(1)
+MCS_ENTRIES_G(2)
+MCS_ENTRIES_G(3)
+MCS_ENTRIES_G(4)
+MCS_MB_ENTRY_G(1)
+MCS_MB_ENTRY_G(2)
+MCS_MB_ENTRY_G(3)
+MCS_MB_ENTRY_G(4)
+MCS_FEATHER_ENTRY(1, 0, _g, true)
+MCS_FEATHER_ENTRY(1, 1, _g, true)
+MCS_FEATHER_ENTRY(2, 0, _g, true)
+MCS_FEATHER_ENTRY(2, 1, _g, true)
+MCS_FEATHER_ENTRY(3, 0, _g, true)
+MCS_FEATHER_ENTRY(3, 1, _g, true)
+MCS_FEATHER_ENTRY(4, 0, _g, true)
+MCS_FEATHER_ENTRY(4, 1, _g, true)

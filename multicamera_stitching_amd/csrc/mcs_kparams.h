@@ -64,6 +64,11 @@ struct KParams {
     const double *lens_tab;
     uint32_t lens_mask;
     int lens_pad_;
+    // Exposure gains of the fused (_g) kernels: q per camera in 1/256, as of the launch (by value:
+    // a launch in flight keeps the gains it was launched with, no device table, no upload).  Read
+    // only by the _g kernels (gain_q_of: a dword of two, scalar for a uniform camera); 32 bytes,
+    // last, so that every other field keeps its kernarg offset.
+    uint16_t gain_q[MCS_MAX_CAMS];
 };
 
 // Kernarg block of the footprint kernel: (KParams, uint8_t* const* masks, u64* counts).

@@ -134,7 +134,7 @@ static int band_form(const mcs_plan *p, const mcs::KParams &P)
 // has one (interior and bottom / right edge bands in ONE launch, blocks below n_in interior, so
 // the edge bands run beside the interior ones), else mb_levels.
 static int launch_mb_levels(const Api *A, const mcs_plan *p, const Kernels *k, mcs::KMbArgs &m,
-                            int f0, int nf, hipStream_t s)
+                            int f0, int nf, hipStream_t s, bool gained)
 {
     m.f0 = f0;
     m.nf = nf;
@@ -147,19 +147,20 @@ static int launch_mb_levels(const Api *A, const mcs_plan *p, const Kernels *k, m
         const int form = band_form(p, b.P);
         const int kind = p->t.n_bands_in == 0 ? 1 : (p->t.n_bands > p->t.n_bands_in ? 2 : 0);
         if (kind == 1) b.band0 = 0;
-        return launch_args(A, k->mb_bands[p->fd.channels][form][kind],
+        return launch_args(A, (gained ? k->mb_bands_g : k->mb_bands)[p->fd.channels][form][kind],
                            xcd_grid((int64_t)p->t.n_bands * gy), 1, mcs::kMbBandLanes, 1, &b,
                            sizeof(b), s);
     }
     const unsigned gz = (unsigned)((nf + mcs::kMbLvFrames - 1) / mcs::kMbLvFrames);
-    return launch_args(A, k->mb_levels[p->fd.channels], (unsigned)p->t.n_blend,
+    return launch_args(A, (gained ? k->mb_levels_g : k->mb_levels)[p->fd.channels],
+                       (unsigned)p->t.n_blend,
                        (unsigned)p->t.mb_slots, mcs::kMbLvThreads, 1, &m, sizeof(m), s, gz);
 }
 
 // Multi-band tiles degraded to the feather rule (more than kBlendSlots owners in their
 // neighbourhood): the feather kernel over d_dense, on stream s after the mosaic is written.
 static int launch_dense(const Api *A, const mcs_plan *p, const Kernels *k, const mcs::KParams &P,
-                        int n_frames, hipStream_t s)
+                        int n_frames, hipStream_t s, bool gained)
 {
     if (p->blend != MCS_BLEND_MULTIBAND || p->t.n_dense <= 0) return MCS_OK;
     mcs::KBlendArgs b;
@@ -168,8 +169,8 @@ static int launch_dense(const Api *A, const mcs_plan *p, const Kernels *k, const
     b.list = p->t.d_dense;
     b.n_frames = n_frames;
     b.pad_ = 0;
-    return launch_args(A, k->feather[p->fd.channels][p->fd.interp], p->t.n_dense, n_frames, 256, 1,
-                       &b, sizeof(b), s);
+    return launch_args(A, (gained ? k->feather_g : k->feather)[p->fd.channels][p->fd.interp],
+                       p->t.n_dense, n_frames, 256, 1, &b, sizeof(b), s);
 }
 
 // The multi-band blend kernel for the plan's owner count (<= 2, <= 4, <= 8 per neighbourhood).
@@ -202,9 +203,11 @@ static int big_parts(bool multiband)
 // One launch (stream over all tiles, + direct over the fallback tiles, + the blend passes) for
 // n_frames captures that share one frame stride.  Work that does not read the mosaic -- the
 // direct-gather tiles and the first multi-band chunk's level pyramids -- runs on two side streams,
-// concurrently with the HBM-bound streaming kernel.
+// concurrently with the HBM-bound streaming kernel.  gained: every kernel of the pair that reads
+// source bytes is its _g twin (stream, big, direct, feather, bands, levels; the multi-band blend
+// reads the mosaic and the scratch) and applies P.gain_q to its taps.
 static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::KParams &P,
-                       int n_frames, hipStream_t s)
+                       int n_frames, hipStream_t s, bool gained)
 {
     // multi-band: the sweep (strips) or the band pass + blend
     const bool sweep = p->blend == MCS_BLEND_MULTIBAND && p->t.n_strips > 0;
@@ -234,7 +237,8 @@ static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::K
         // each large-footprint tile as `parts` blocks over capture ranges: one block per CU per
         // tile otherwise streams the whole batch and sets the launch's tail (C4: 31 tiles)
         bg.parts = std::max(1, std::min(big_parts(mb || sweep), n_frames));
-        return launch_args(A, k->stream_big[p->fd.channels][b32 ? 1 : 0],
+        const auto &big = gained ? k->stream_big_g : k->stream_big;
+        return launch_args(A, big[p->fd.channels][b32 ? 1 : 0],
                            8u * (((unsigned)(p->t.n_big * bg.parts) + 7u) / 8u), 1, mcs::kWave,
                            mcs::kWavesPerBlock, &bg, sizeof(bg), q, 1,
                            (unsigned)mcs::kBigStreamLds);
@@ -251,9 +255,9 @@ static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::K
         da.n_frames = n_frames;
         da.pad_ = 0;
         const unsigned gy = (unsigned)((n_frames + mcs::kDirectFrames - 1) / mcs::kDirectFrames);
-        const int rc = launch_args(A, k->direct[p->fd.channels][p->fd.interp][off32 ? 1 : 0],
-                                   p->t.n_fallback, gy, mcs::kWave, mcs::kWavesPerBlock, &da,
-                                   sizeof(da), p->side);
+        const int rc = launch_args(
+            A, (gained ? k->direct_g : k->direct)[p->fd.channels][p->fd.interp][off32 ? 1 : 0],
+            p->t.n_fallback, gy, mcs::kWave, mcs::kWavesPerBlock, &da, sizeof(da), p->side);
         if (rc) return rc;
     }
     if (aside) HIP_TRY(A->hipEventRecord(p->ev_join, p->side));
@@ -284,7 +288,8 @@ static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::K
     }
     if (mb) {
         HIP_TRY(A->hipStreamWaitEvent(p->side2, p->ev_fork, 0));
-        int rc = launch_mb_levels(A, p, k, m, 0, std::min(p->t.mb_chunk, n_frames), p->side2);
+        int rc = launch_mb_levels(A, p, k, m, 0, std::min(p->t.mb_chunk, n_frames), p->side2,
+                                  gained);
         if (rc) return rc;
         if (!split) HIP_TRY(A->hipEventRecord(p->ev_join2, p->side2));
     }
@@ -294,8 +299,9 @@ static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::K
         args.order = order;
         args.n_order = n_items;
         const unsigned grid = 8u * (((unsigned)n_items + 7u) / 8u);
-        return launch_args(A, k->stream[p->fd.channels][b32 ? 1 : 0], grid, 1, mcs::kWave,
-                           mcs::kWavesPerBlock, &args, sizeof(args), s, 1, lds);
+        return launch_args(A, (gained ? k->stream_g : k->stream)[p->fd.channels][b32 ? 1 : 0],
+                           grid, 1, mcs::kWave, mcs::kWavesPerBlock, &args, sizeof(args), s, 1,
+                           lds);
     };
     if (split) {
         int rc = stream_launch(p->t.d_order, p->t.n_early);
@@ -312,7 +318,7 @@ static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::K
         }
         if (aside) HIP_TRY(A->hipStreamWaitEvent(s, p->ev_join, 0));
         HIP_TRY(A->hipStreamWaitEvent(s, p->ev_join2, 0));
-        return launch_dense(A, p, k, P, n_frames, s);
+        return launch_dense(A, p, k, P, n_frames, s, gained);
     }
     {
         // (d_order: the tile order of prepare / prepare_bands; NULL: row-major grid order)
@@ -332,20 +338,20 @@ static int launch_pair(const Api *A, const mcs_plan *p, const Kernels *k, mcs::K
             b.list = p->t.d_blist;
             b.n_frames = n_frames;
             b.pad_ = 0;
-            rc = launch_args(A, k->feather[p->fd.channels][p->fd.interp], p->t.n_blend, n_frames,
-                             256, 1, &b, sizeof(b), s);
+            rc = launch_args(A, (gained ? k->feather_g : k->feather)[p->fd.channels][p->fd.interp],
+                             p->t.n_blend, n_frames, 256, 1, &b, sizeof(b), s);
         } else {
             // multi-band: per chunk of captures (scratch stride mb_chunk) levels (chunk 0's
             // already ran on the side stream) then blend
             for (int f0 = 0; f0 < n_frames && rc == MCS_OK; f0 += p->t.mb_chunk) {
                 const int nf = std::min(p->t.mb_chunk, n_frames - f0);
-                if (f0 > 0) rc = launch_mb_levels(A, p, k, m, f0, nf, s);
+                if (f0 > 0) rc = launch_mb_levels(A, p, k, m, f0, nf, s, gained);
                 if (rc == MCS_OK) rc = launch_mb_blend(A, p, k, m, f0, nf, s);
             }
         }
         if (rc) return rc;
     }
-    return launch_dense(A, p, k, P, n_frames, s);
+    return launch_dense(A, p, k, P, n_frames, s, gained);
 }
 
 // Side streams + fork/join events for the direct-gather tiles and the multi-band levels (created
@@ -404,7 +410,24 @@ int launch_resize(const Api *A, const Kernels *k, const uint8_t *src, int sw, in
                        mcs::kResizeBlock, 1, &a, sizeof(a), s, n_frames);
 }
 
-int launch_stitch(const Api *A, mcs_plan *p, const mcs::KParams &kp, int n_frames, hipStream_t s)
+bool gains_active(const mcs_plan *p)
+{
+    if (!p->gains_on) return false;
+    bool need[MCS_MAX_CAMS];
+    need_mask(p->fd, need);
+    for (int i = 0; i < p->fd.n_cams; i++)
+        if (need[i] && p->gain_q[i] != 256) return true;
+    return false;
+}
+
+void fill_gain_q(const mcs_plan *p, mcs::KParams *kp)
+{
+    for (int i = 0; i < MCS_MAX_CAMS; i++)
+        kp->gain_q[i] = p->gains_on && i < p->fd.n_cams ? p->gain_q[i] : (uint16_t)256;
+}
+
+int launch_stitch(const Api *A, mcs_plan *p, const mcs::KParams &kp, int n_frames, hipStream_t s,
+                  bool gained)
 {
     if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames <= 0) return MCS_OK;
     const Kernels *k = nullptr;
@@ -423,12 +446,21 @@ int launch_stitch(const Api *A, mcs_plan *p, const mcs::KParams &kp, int n_frame
     P.map_tab = p->kp.map_tab;   // (table plans)
     P.lens_tab = p->kp.lens_tab; // (lensed plans)
     P.skip = p->kp.skip;         // (multi-band sweep plans: set by prepare)
-    if (uniform) return launch_pair(A, p, k, P, n_frames, s);
+    if (gained) {
+        // (the sweep kernel has no _g twin: its pixels would come out ungained)
+        if (p->t.n_strips > 0)
+            return mcs::fail(MCS_E_UNSUPPORTED,
+                             "the plan's multi-band tables were prepared for the sweep "
+                             "(MCS_MB_SWEEP=1), whose kernel has no fused-gain variant: apply the "
+                             "gains with mcs_gain_apply_device, or prepare without the sweep");
+        fill_gain_q(p, &P);     // by value in every launch's arguments: the gains as of this call
+    }
+    if (uniform) return launch_pair(A, p, k, P, n_frames, s, gained);
     for (int f = 0; f < n_frames; f++) {
         for (int i = 0; i < p->fd.n_cams; i++)
             P.cams[i] = kp.cams[i] ? kp.cams[i] + (int64_t)f * kp.cam_fstride[i] : nullptr;
         P.out = kp.out + (int64_t)f * kp.out_fstride;
-        rc = launch_pair(A, p, k, P, 1, s);
+        rc = launch_pair(A, p, k, P, 1, s, gained);
         if (rc) return rc;
     }
     return MCS_OK;

@@ -188,6 +188,15 @@ struct Kernels {
     hipFunction_t overlap_prep[2] = {};   // [interp]
     hipFunction_t overlap_sum[5] = {};    // [channels]
     hipFunction_t gain_apply = nullptr;
+    // the fused-gain twins (suffix _g: the camera gains of KParams::gain_q on the taps) of every
+    // kernel that reads source bytes per launch, indexed as their twins.  (mb_blend has none: it
+    // reads the mosaic and the level scratch.)
+    hipFunction_t stream_g[5][2] = {};
+    hipFunction_t stream_big_g[5][2] = {};
+    hipFunction_t direct_g[5][2][2] = {};
+    hipFunction_t feather_g[5][2] = {};
+    hipFunction_t mb_levels_g[5] = {};
+    hipFunction_t mb_bands_g[5][2][3] = {};
 };
 
 // mcs_prepare.cpp
@@ -230,7 +239,15 @@ void band_args(const mcs_plan *p, const KParams &P, KMbBandArgs &a);
 int launch_resize(const Api *A, const Kernels *k, const uint8_t *src, int sw, int sh,
                   int64_t src_pitch, int64_t src_fstride, uint8_t *dst, int dw, int dh,
                   int64_t dst_pitch, int64_t dst_fstride, int C, int n_frames, hipStream_t s);
-int launch_stitch(const Api *A, mcs_plan *p, const KParams &kp, int n_frames, hipStream_t s);
+// gained: the _g kernels for every launch of the batch, with the plan's gain_q as of this call in
+// their kernel arguments (mcs_stitch_device_gained); the caller has ruled out sweep plans.
+int launch_stitch(const Api *A, mcs_plan *p, const KParams &kp, int n_frames, hipStream_t s,
+                  bool gained = false);
+// Whether a gained launch of the plan needs the _g kernels: gains enabled and some used camera's
+// q other than 256 (q = 256 is the identity bit for bit: the ungained kernels are exact).
+bool gains_active(const mcs_plan *p);
+// The plan's q per camera into kp.gain_q (256 where gains are disabled).
+void fill_gain_q(const mcs_plan *p, KParams *kp);
 
 }  // namespace host
 }  // namespace mcs

@@ -35,6 +35,14 @@ int kernels(const Api *A, int device, const Kernels **out)
             if (rc == MCS_OK) rc = fn(name, &k.stream_big[c][0]);
             snprintf(name, sizeof(name), "mcs_stream_big_c%d_b32", c);
             if (rc == MCS_OK) rc = fn(name, &k.stream_big[c][1]);
+            for (int b = 0; b < 2; b++) {   // the fused-gain twins
+                snprintf(name, sizeof(name), "mcs_stream_c%d%s_g", c, b ? "_b32" : "");
+                if (rc == MCS_OK) rc = fn(name, &k.stream_g[c][b]);
+                snprintf(name, sizeof(name), "mcs_stream_big_c%d%s_g", c, b ? "_b32" : "");
+                if (rc == MCS_OK) rc = fn(name, &k.stream_big_g[c][b]);
+            }
+            snprintf(name, sizeof(name), "mcs_mb_levels_c%d_g", c);
+            if (rc == MCS_OK) rc = fn(name, &k.mb_levels_g[c]);
             snprintf(name, sizeof(name), "mcs_resize_c%d", c);
             if (rc == MCS_OK) rc = fn(name, &k.resize[c]);
             snprintf(name, sizeof(name), "mcs_mb_levels_c%d", c);
@@ -47,6 +55,12 @@ int kernels(const Api *A, int device, const Kernels **out)
                 if (rc == MCS_OK) rc = fn(name, &k.mb_bands[c][al][1]);
                 snprintf(name, sizeof(name), "mcs_mb_bands_all%s_c%d", sfx, c);
                 if (rc == MCS_OK) rc = fn(name, &k.mb_bands[c][al][2]);
+                snprintf(name, sizeof(name), "mcs_mb_bands%s_c%d_g", sfx, c);
+                if (rc == MCS_OK) rc = fn(name, &k.mb_bands_g[c][al][0]);
+                snprintf(name, sizeof(name), "mcs_mb_bands_br%s_c%d_g", sfx, c);
+                if (rc == MCS_OK) rc = fn(name, &k.mb_bands_g[c][al][1]);
+                snprintf(name, sizeof(name), "mcs_mb_bands_all%s_c%d_g", sfx, c);
+                if (rc == MCS_OK) rc = fn(name, &k.mb_bands_g[c][al][2]);
             }
             snprintf(name, sizeof(name), "mcs_mb_blend_c%d_s2", c);
             if (rc == MCS_OK) rc = fn(name, &k.mb_blend[c][0]);
@@ -59,6 +73,8 @@ int kernels(const Api *A, int device, const Kernels **out)
                 rc = fn(name, &k.prepare[c][i]);
                 snprintf(name, sizeof(name), "mcs_feather_c%d_i%d", c, i);
                 if (rc == MCS_OK) rc = fn(name, &k.feather[c][i]);
+                snprintf(name, sizeof(name), "mcs_feather_c%d_i%d_g", c, i);
+                if (rc == MCS_OK) rc = fn(name, &k.feather_g[c][i]);
                 snprintf(name, sizeof(name), "mcs_mb_prep_c%d_i%d", c, i);
                 if (rc == MCS_OK) rc = fn(name, &k.mb_prep[c][i]);
                 snprintf(name, sizeof(name), "mcs_mb_bdesc_c%d_i%d", c, i);
@@ -68,6 +84,8 @@ int kernels(const Api *A, int device, const Kernels **out)
                 for (int o = 0; o < 2 && rc == MCS_OK; o++) {
                     snprintf(name, sizeof(name), "mcs_direct_c%d_i%d_o%d", c, i, o ? 32 : 64);
                     rc = fn(name, &k.direct[c][i][o]);
+                    snprintf(name, sizeof(name), "mcs_direct_c%d_i%d_o%d_g", c, i, o ? 32 : 64);
+                    if (rc == MCS_OK) rc = fn(name, &k.direct_g[c][i][o]);
                 }
             }
         }

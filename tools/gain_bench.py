@@ -5,13 +5,20 @@
   stats  mcs_plan_overlap_stats over the 64 captures per grid step (accumulator memset, the
          mcs_overlap_sum launch, the copy back of S): HIP events around the call, and its wall time;
   apply  mcs_gain_apply_device over every camera's 64 frames, in place (reads and writes every
-         source byte once), with the bandwidth that makes.
+         source byte once), with the bandwidth that makes;
+  fused  per blend mode (paste, multi-band) the launch of the 64 captures three ways, alternated
+         step by step: (a) mcs_stitch_device of an ungained plan, (b) mcs_stitch_device_gained with
+         gains other than the identity on all four cameras, (c) what a caller without the fused
+         entry point does: mcs_gain_apply_device on all cameras in place (on scratch copies of the
+         frames, refreshed outside the timed region), then (a) on them.  b - a is what the fused
+         gains cost, c - a what the separate pass costs.
 
 Warm-up rounds, then --steps event-timed repeats; median, min, max and interquartile range.  A
 step whose table passes the library's 64 MiB limit is reported as refused.  Prints the lines and,
 with --out, writes them to a file.
 
     python tools/gain_bench.py --steps 20 --out profiles/gain_bench.txt
+    python tools/gain_bench.py --sections fused --out profiles/gain_fused_bench.txt
 """
 import argparse
 import json
@@ -31,6 +38,75 @@ def spread(ms):
             "ms_max": round(float(ms.max()), 4), "ms_iqr": round(float(q3 - q1), 4)}
 
 
+def fused(args, torch, _capi, st, _stage_desc, d_cams, stream):
+    """The fused lines: per blend mode the variants a, b, c alternated step by step."""
+    n, w, h, C, F = 4, args.width, args.height, 3, args.frames
+    gains = [1.37, 0.83, 1.21, 0.61]
+    descs = [_stage_desc(sb) for sb in st.stitchers]
+    scratch = [torch.empty_like(t) for t in d_cams]
+    ptrs = [t.data_ptr() for t in d_cams]
+    sptrs = [t.data_ptr() for t in scratch]
+    strides = [t[0].numel() for t in d_cams]
+    q = [min(max(int(np.rint(256.0 * g)), 1), 65535) for g in gains]
+    out_lines = []
+    for name, mode in (("paste", 0), ("multiband", 2)):
+        plain = _capi.Plan(descs, w, h, C, _capi.MCS_INTER_LINEAR)
+        gained = _capi.Plan(descs, w, h, C, _capi.MCS_INTER_LINEAR)
+        if mode:
+            plain.set_blend(mode)
+            gained.set_blend(mode)
+        gained.set_gains(gains)
+        pitch = (plain.out_w * C + 255) // 256 * 256
+        out = torch.empty((F, plain.out_h, pitch), dtype=torch.uint8, device=d_cams[0].device)
+
+        def a(src=ptrs):
+            plain.stitch_device(src, strides, out.data_ptr(), pitch, out[0].numel(), F,
+                                stream.cuda_stream)
+
+        def b():
+            gained.stitch_device_gained(ptrs, strides, out.data_ptr(), pitch, out[0].numel(), F,
+                                        stream.cuda_stream)
+
+        def c():
+            for t, qi in zip(scratch, q):
+                _capi.gain_apply_device(t.data_ptr(), t.data_ptr(), t[0].numel(), qi, F, 0, 0, 0,
+                                        stream.cuda_stream)
+            a(sptrs)
+
+        def refresh():
+            with torch.cuda.stream(stream):
+                for t, src in zip(scratch, d_cams):
+                    t.copy_(src)
+
+        variants = (("a_stitch_device", a), ("b_stitch_device_gained", b),
+                    ("c_apply_then_stitch_device", c))
+        ev = {k: [] for k, _ in variants}
+        for i in range(args.warmup + args.steps):
+            for k, fn in variants:
+                refresh()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                fn()
+                e1.record(stream)
+                if i >= args.warmup:
+                    ev[k].append((e0, e1))
+        torch.cuda.synchronize()
+        line = {"fused": name, "gains_q": q}
+        for k, _ in variants:
+            line[k] = spread([e0.elapsed_time(e1) for e0, e1 in ev[k]])
+        line["b_minus_a_ms"] = round(line["b_stitch_device_gained"]["ms_median"] -
+                                     line["a_stitch_device"]["ms_median"], 4)
+        line["c_minus_a_ms"] = round(line["c_apply_then_stitch_device"]["ms_median"] -
+                                     line["a_stitch_device"]["ms_median"], 4)
+        line["b_median_below_c_min"] = bool(line["b_stitch_device_gained"]["ms_median"] <
+                                            line["c_apply_then_stitch_device"]["ms_min"])
+        out_lines.append(line)
+        plain.close()
+        gained.close()
+        del out
+    return out_lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -39,6 +115,8 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--grid-steps", type=int, nargs="*", default=[0, 1, 2])
+    ap.add_argument("--sections", nargs="*", default=["stats", "apply", "fused"],
+                    choices=["stats", "apply", "fused"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -64,7 +142,7 @@ def main():
               "mosaic": [plan.out_w, plan.out_h], "steps": args.steps, "warmup": args.warmup,
               "build_id": _capi.build_id(), "device": torch.cuda.get_device_name(0)}]
 
-    for k in args.grid_steps:
+    for k in (args.grid_steps if "stats" in args.sections else []):
         def call():
             t0 = time.perf_counter()
             N, _ = plan.overlap_stats(ptrs, strides, F, k, stream.cuda_stream)
@@ -98,21 +176,26 @@ def main():
         for t in d_cams:
             _capi.gain_apply_device(t.data_ptr(), t.data_ptr(), t[0].numel(), 300, F, 0, 0, 0,
                                     stream.cuda_stream)
-    for _ in range(args.warmup):
-        apply()
-    torch.cuda.synchronize()
-    ev = []
-    for _ in range(args.steps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        apply()
-        b.record(stream)
-        ev.append((a, b))
-    torch.cuda.synchronize()
-    s = spread([a.elapsed_time(b) for a, b in ev])
-    nbytes = sum(t.numel() for t in d_cams)
-    lines.append({"apply_all_cameras_in_place": s, "source_bytes": nbytes,
-                  "read_plus_write_tb_per_s": round(2 * nbytes / (s["ms_median"] * 1e-3) / 1e12, 3)})
+    if "apply" in args.sections:
+        for _ in range(args.warmup):
+            apply()
+        torch.cuda.synchronize()
+        ev = []
+        for _ in range(args.steps):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            apply()
+            b.record(stream)
+            ev.append((a, b))
+        torch.cuda.synchronize()
+        s = spread([a.elapsed_time(b) for a, b in ev])
+        nbytes = sum(t.numel() for t in d_cams)
+        lines.append({"apply_all_cameras_in_place": s, "source_bytes": nbytes,
+                      "read_plus_write_tb_per_s":
+                          round(2 * nbytes / (s["ms_median"] * 1e-3) / 1e12, 3)})
+
+    if "fused" in args.sections:
+        lines += fused(args, torch, _capi, st, _stage_desc, d_cams, stream)
 
     text = "\n".join(json.dumps(line) for line in lines)
     print(text)
