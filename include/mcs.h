@@ -102,7 +102,10 @@ const char *mcs_hip_runtime(void);
  * StitcherBase, :190-209).  cam0_w/cam0_h: calibrated size of the first camera (B of stage 0).
  * channels: 1..4 (interleaved u8, e.g. BGR = 3).  interp: MCS_INTER_LINEAR is the reference
  * default (:239); MCS_INTER_NEAREST is the north-star C1 variant.  device: HIP ordinal.
- * Host-side only: no device memory is touched until the first stitch call. */
+ * Host-side only: no device memory is touched until the first stitch call.
+ * Smallest frame: every camera frame of every plan kind (chain, cylindrical, warp, undistort) has
+ * at least 8 bytes, w * h * channels >= 8 -- the kernels read 8-byte windows that end inside the
+ * frame; a smaller one is refused at plan creation with MCS_E_UNSUPPORTED. */
 int mcs_plan_create(const mcs_stage_desc *stages, int n_stages, int cam0_w, int cam0_h,
                     int channels, int interp, int device, mcs_plan **out);
 /* A camera of a rotation-only rig projected onto a cylinder (SURVEY.md section 8 NS-6 / C4:

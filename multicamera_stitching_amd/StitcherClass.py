@@ -547,20 +547,27 @@ def _note_orb_fallback(owner):
 
 # C-ABI statuses (include/mcs.h) _run_chain turns into a logged fallback image: run-time failures
 # of the device.  The capacity limits -- inputs the reference handles but the kernels do not
-# (more cameras than MCS_MAX_CAMS, a channel count outside 1-4) -- are checked before the call
-# (_capacity_exceeded) and take the same logged fallback; every other status, MCS_E_UNSUPPORTED
-# included (API misuse), raises.  (More than 8 cameras meeting in one multi-band neighbourhood is
-# not an error: those tiles take the feather rule on the GPU.)
+# (more cameras than MCS_MAX_CAMS, a channel count outside 1-4, a calibrated frame under 8 bytes)
+# -- are checked before the call (_capacity_exceeded) and take the same logged fallback; every
+# other status, MCS_E_UNSUPPORTED included (API misuse), raises.  (More than 8 cameras meeting in
+# one multi-band neighbourhood is not an error: those tiles take the feather rule on the GPU.)
 _RUNTIME_FAILURES = (_capi.MCS_E_HIP, _capi.MCS_E_NOMEM)
 
 
-def _capacity_exceeded(cams):
-    """Why the kernels cannot take these camera images (None when they can)."""
+def _capacity_exceeded(cams, chain=(), cam0_hw=None):
+    """Why the kernels cannot take these camera images (None when they can).  chain, cam0_hw: the
+    calibrated frame sizes the plan is built for (the images are resized to them)."""
     if len(cams) > _capi.MCS_MAX_CAMS:
         return "{} cameras (at most {})".format(len(cams), _capi.MCS_MAX_CAMS)
     c = _channels(cams[0]) if cams else 1
     if not 1 <= c <= 4:
         return "{} channels (1-4)".format(c)
+    # include/mcs.h "Smallest frame": the kernels read 8-byte windows that end inside the frame
+    sizes = [tuple(cam0_hw)] if cam0_hw is not None else []
+    sizes += [tuple(sb.AimgSize[:2]) for sb in chain if sb.cachedAH is not None]
+    for h, w in sizes:
+        if int(h) * int(w) * c < 8:
+            return "a {}x{} camera frame of {} bytes (at least 8)".format(w, h, int(h) * int(w) * c)
     return None
 
 
@@ -568,13 +575,15 @@ def _run_chain(owner, chain, cams, fallback):
     """One GPU stitch of the chain.  The reference never raises on an expected failure: it logs
     and returns a fallback image (:126-128 the last camera's image, :255-256 B).  A failure of
     the GPU path at run time (MCS_E_HIP, MCS_E_NOMEM: a device allocation or launch that fails) or
-    an input the reference handles but these kernels do not (MCS_E_UNSUPPORTED: more cameras than
-    MCS_MAX_CAMS, a channel count outside 1-4) is logged the same way and `fallback` is returned --
-    the caller's thread (Qt GUI / worker) gets an image, never an exception, and the log says why.
-    Argument and programming errors (MCS_E_INVALID, MCS_E_SHAPE) are raised: the reference has no
-    catch for them either.  (There is no CPU stitch behind it: a missing libmcs.so fails at import.)"""
+    an input the reference handles but these kernels do not (_capacity_exceeded, checked before
+    any libmcs call: more cameras than MCS_MAX_CAMS, a channel count outside 1-4, a calibrated
+    camera frame under 8 bytes) is logged the same way and `fallback` is returned -- the caller's
+    thread (Qt GUI / worker) gets an image, never an exception, and the log says why.  Argument and
+    programming errors (MCS_E_INVALID, MCS_E_SHAPE, and MCS_E_UNSUPPORTED from the call itself) are
+    raised: the reference has no catch for them either.  (There is no CPU stitch behind it: a
+    missing libmcs.so fails at import.)"""
     cams, cam0_hw, sizes = _conform_cameras(owner, chain, cams)
-    why = _capacity_exceeded(cams)
+    why = _capacity_exceeded(cams, chain, cam0_hw)
     if why is not None:
         owner.debugger(DEBUG_LEVEL_0, "[STITCHER] GPU stitch unsupported ({}); returning the "
                        "fallback image".format(why), log_type="err")

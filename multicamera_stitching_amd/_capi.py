@@ -111,6 +111,35 @@ class FlatDesc(ctypes.Structure):
     ]
 
 
+# csrc/mcs_kparams.h: the streaming tile grid and the prepared per-tile tables (Plan.tile_tables)
+TILE_W, TILE_H, TILE_PX_PER_LANE = 128, 16, 4
+TILE_CAMS = 4
+TILE_MAX_JOBS = 128
+TILE_DESC_WORDS = 3
+LDS_SLACK = 16
+
+
+class TileHdr(ctypes.Structure):
+    """mcs::TileHdr (csrc/mcs_kparams.h), 128 bytes."""
+    _fields_ = [
+        ("fits", ctypes.c_int),
+        ("ncam", ctypes.c_int),
+        ("njobs", ctypes.c_int),
+        ("ring", ctypes.c_int),
+        ("buf_bytes", ctypes.c_int),
+        ("cam", ctypes.c_int * TILE_CAMS),
+        ("rmin", ctypes.c_int * TILE_CAMS),
+        ("cal", ctypes.c_int * TILE_CAMS),
+        ("stride", ctypes.c_int * TILE_CAMS),
+        ("base", ctypes.c_int * TILE_CAMS),
+        ("jobstart", ctypes.c_int * (TILE_CAMS + 1)),
+        ("last_shift", ctypes.c_int),
+        ("pad_", ctypes.c_int),
+    ]
+
+
+assert ctypes.sizeof(TileHdr) == 128
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -309,6 +338,8 @@ def load() -> ctypes.CDLL:
         L.mcs_gain_apply_device.restype = I
         L.mcs__force_off64.argtypes = [I]   # test hook (not part of mcs.h)
         L.mcs__force_off64.restype = None
+        L.mcs__plan_tile_tables.argtypes = [P, P, P, P, I]   # test hook (not part of mcs.h)
+        L.mcs__plan_tile_tables.restype = I
         if L.mcs_abi_version() != ABI_VERSION:
             raise ImportError(f"libmcs ABI {L.mcs_abi_version()} != expected {ABI_VERSION}")
         _lib = L
@@ -550,6 +581,24 @@ class Plan:
     def prepare(self, stream: int = 0):
         """Evaluate and store the plan's map tables on its device (once)."""
         check(self._lib.mcs_plan_prepare(self._h, ctypes.c_void_p(int(stream))))
+
+    def tile_tables(self):
+        """Test hook mcs__plan_tile_tables: the prepared streaming tables of the plan (call
+        prepare() first) as (tiles, spans, desc) -- a ctypes array of TileHdr, the row spans
+        (n_tiles, TILE_MAX_JOBS) uint16 and the full-form descriptors
+        (n_tiles, TILE_W * TILE_H, TILE_DESC_WORDS) uint32, pixels in thread-major order."""
+        n = self._lib.mcs__plan_tile_tables(self._h, None, None, None, 0)
+        if n < 0:
+            check(n)
+        tiles = (TileHdr * max(n, 1))()
+        spans = np.zeros((n, TILE_MAX_JOBS), np.uint16)
+        desc = np.zeros((n, TILE_W * TILE_H, TILE_DESC_WORDS), np.uint32)
+        if n:
+            rc = self._lib.mcs__plan_tile_tables(self._h, ctypes.byref(tiles), spans.ctypes.data,
+                                                 desc.ctypes.data, n)
+            if rc < 0:
+                check(rc)
+        return tiles, spans, desc
 
     def stats(self) -> dict:
         arr = (ctypes.c_int64 * 21)()

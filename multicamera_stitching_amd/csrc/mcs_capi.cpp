@@ -122,6 +122,9 @@ int mcs_plan_create_cylindrical(const mcs_cyl_camera *cams, int n_cams, int out_
         const mcs_cyl_camera &k = cams[c];
         if (k.w < 1 || k.h < 1 || k.w > 32767 || k.h > 32767)
             return mcs::fail(MCS_E_SHAPE, "camera %d: %dx%d", c, k.w, k.h);
+        if ((long)k.w * k.h * channels < 8)
+            return mcs::fail(MCS_E_UNSUPPORTED, "camera %d: camera frame of %ld bytes (< 8)", c,
+                             (long)k.w * k.h * channels);
         bool fin = std::isfinite(k.f) && k.f > 0.0 && std::isfinite(k.cx) && std::isfinite(k.cy);
         for (double r : k.R) fin = fin && std::isfinite(r);
         if (!fin) return mcs::fail(MCS_E_INVALID, "camera %d: R / f / cx / cy", c);
@@ -205,6 +208,10 @@ int check_single_args(int src_w, int src_h, int dst_w, int dst_h, int channels, 
     if (channels < 1 || channels > 4) return mcs::fail(MCS_E_INVALID, "channels %d", channels);
     if (src_w < 1 || src_h < 1 || src_w > 32767 || src_h > 32767)
         return mcs::fail(MCS_E_SHAPE, "source %dx%d", src_w, src_h);
+    // (the direct gather moves each 8-byte window left so that it ends inside the frame)
+    if ((long)src_w * src_h * channels < 8)
+        return mcs::fail(MCS_E_UNSUPPORTED, "camera frame of %ld bytes (< 8)",
+                         (long)src_w * src_h * channels);
     if (dst_w < 1 || dst_h < 1 || (int64_t)dst_w * dst_h * channels > ((int64_t)1 << 31))
         return mcs::fail(MCS_E_SHAPE, "destination %dx%d", dst_w, dst_h);
     return MCS_OK;
@@ -937,3 +944,36 @@ int mcs_plan_footprint(mcs_plan *p, int64_t *touched_px, int n_cams)
 }
 
 }  // extern "C"
+
+// Test hook (not in mcs.h): the prepared streaming tables of a plan, copied to host buffers --
+// tiles_out: TileHdr per tile, spans_out: kMaxTileJobs u16 per tile, desc_out: the full-form
+// descriptors, kTilePx * kDescWords u32 per tile.  Returns the tile count (the buffers are filled
+// only when all three are given and max_tiles holds it), or a negative status: the plan must be
+// prepared (mcs_plan_prepare).  Reads only: the plan and its tables stay as they are.
+extern "C" int mcs__plan_tile_tables(const mcs_plan *p, void *tiles_out, uint16_t *spans_out,
+                                     uint32_t *desc_out, int max_tiles)
+{
+    mcs::clear_error();
+    if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
+    if (!p->t.prepared) return mcs::fail(MCS_E_INVALID, "the plan is not prepared");
+    const Api *A = mcs::rt::api();
+    if (!A) return MCS_E_HIP;
+    const size_t tiles = (size_t)p->gx * p->gy;
+    if (!tiles_out || !spans_out || !desc_out || (size_t)std::max(max_tiles, 0) < tiles ||
+        tiles == 0)
+        return (int)tiles;
+    DeviceGuard g(A, p->device);
+    if (g.err != hipSuccess)
+        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    // (prepare synchronised after building them; the copies run on the null stream)
+    HIP_TRY(A->hipMemcpyAsync(tiles_out, p->t.d_tiles, tiles * sizeof(mcs::TileHdr),
+                              hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(A->hipMemcpyAsync(spans_out, p->t.d_spans,
+                              tiles * mcs::kMaxTileJobs * sizeof(uint16_t), hipMemcpyDeviceToHost,
+                              nullptr));
+    HIP_TRY(A->hipMemcpyAsync(desc_out, p->t.d_desc,
+                              tiles * mcs::kTilePx * mcs::kDescWords * sizeof(uint32_t),
+                              hipMemcpyDeviceToHost, nullptr));
+    HIP_TRY(A->hipStreamSynchronize(nullptr));
+    return (int)tiles;
+}

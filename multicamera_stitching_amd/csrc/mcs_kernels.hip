@@ -415,6 +415,15 @@ __device__ __forceinline__ void prepare_tile(const KParams &P, TileHdr *tiles, u
                 if (e > 255 || (int64_t)fl.rmax[c] * pitch + cal - e < 0) fits = 0;
                 else shifts |= e << (8 * n);
             }
+            // ... and so must the chunks of every other footprint row, which are fetched where
+            // they lie: a row's windows span at most `need` bytes from cal.  (Only rows shorter
+            // than 8 bytes can fail this -- a 16-byte chunk of row h - 2 then ends past the frame;
+            // such tiles take the direct gather.)
+            const int need = (fl.cmax[c] + 2 * CN - cal + 15) & ~15;
+            const int r_hi = min(fl.rmax[c], P.cam_h[c] - 2);
+            if (r_hi >= fl.rmin[c] &&
+                (int64_t)r_hi * pitch + cal + need > (int64_t)pitch * P.cam_h[c])
+                fits = 0;
             n++;
         }
         for (int k = n; k < kTileCams; k++) {
@@ -512,8 +521,10 @@ constexpr int kDmaAux = 0;
 // Block-uniform value read from LDS (broadcast read + readfirstlane -> SGPR).
 __device__ __forceinline__ int uni(const int &v) { return __builtin_amdgcn_readfirstlane(v); }
 
-// The LDS-DMA jobs of one wave, resolved once per block.  Every chunk lies inside its camera frame
-// (TileHdr::last_shift).
+// The LDS-DMA jobs of one wave, resolved once per block.  Every chunk lies inside its camera frame:
+// prepare_tile keeps a tile on this path only when the frame's last row can be fetched from
+// earlier bytes (TileHdr::last_shift) and every other footprint row's chunks end inside the frame
+// (tests/test_gpu_tile_tables.py restates this arithmetic and checks every chunk).
 //   BUF (every byte of every capture of every used camera within 4 GiB of P.base): offsets from
 //   P.base, read through one buffer resource (buffer_load_dwordx4 ... offen lds), the capture's
 //   offset f * fstride in the instruction's scalar offset -- no per-row 64-bit address math;

@@ -137,6 +137,29 @@ def test_capacity_limits_take_the_fallback(monkeypatch, caplog):
     assert sc._capacity_exceeded([np.zeros((4, 4, 3), np.uint8)] * 3) is None
 
 
+def test_sub_8_byte_frames_take_the_fallback(monkeypatch, caplog):
+    """A rig of 2 x 2 gray frames (4 bytes each: libmcs refuses camera frames under 8 bytes with
+    MCS_E_UNSUPPORTED) is logged and the fallback image returned, before any libmcs call -- never
+    an exception in the caller's thread (advisor finding, round 6)."""
+    from multicamera_stitching_amd import StitcherClass as sc
+    imgs = {k: np.full((2, 2), 10 + i, np.uint8) for i, k in enumerate(rig.labels(3))}
+    st = Stitcher(imgs)
+    st.calibrate_stitcher(imgs, save=False, homographies=[[[1, 0, 1], [0, 1, 0], [0, 0, 1]],
+                                                          [[1, 0, 2], [0, 1, 0], [0, 0, 1]]])
+    assert all(s.cachedAH is not None for s in st.stitchers)
+    called = []
+    monkeypatch.setattr(sc, "_get_plan", lambda *a, **k: called.append(1))
+    with caplog.at_level(logging.ERROR, logger="multicamera_stitching_amd"):
+        out = st.stitch(imgs)
+    assert isinstance(out, np.ndarray) and not called
+    assert "unsupported (a 2x2 camera frame of 4 bytes" in caplog.text
+    # the limit is the frame's bytes: 2 x 2 BGRA (16 bytes) and 8 x 1 gray (8) pass the check
+    big = [np.zeros((2, 2, 4), np.uint8)] * 3
+    assert sc._capacity_exceeded(big, st.stitchers, (2, 2)) is None
+    assert sc._capacity_exceeded([np.zeros((1, 8), np.uint8)] * 3, (), (1, 8)) is None
+    assert sc._capacity_exceeded([np.zeros((1, 7), np.uint8)] * 3, (), (1, 7)) is not None
+
+
 def test_failed_homography_resets_stage():
     imgs = images()
     st = Stitcher(imgs)
