@@ -263,8 +263,11 @@ int mcs_stitch_device(mcs_plan *plan, const uint8_t *const *d_cams,
  * OpenCV map in the kernel itself (the direct-gather kernel over all tiles), so a plan is
  * usable the moment mcs_plan_create returns (host flattening only, microseconds) -- the path for
  * geometry that changes every capture (per-frame homographies, SURVEY.md 8 C3: estimate ->
- * stitch).  Paste (MCS_BLEND_NONE) and MCS_BLEND_SEAM plans; the same pixels as
- * mcs_stitch_device, lensed plans (mcs_plan_set_lens) included.  Replaces, per capture,
+ * stitch).  Paste (MCS_BLEND_NONE), MCS_BLEND_SEAM and MCS_BLEND_FEATHER plans, chain or
+ * cylindrical; the same pixels as mcs_stitch_device, lensed plans (mcs_plan_set_lens) and seam
+ * hints (mcs_plan_find_seams) included.  FEATHER is one pass over the mosaic (every slot's map,
+ * sum d I / sum d per pixel: no owner pass, no tile lists, any number of contributors per
+ * pixel).  MCS_BLEND_MULTIBAND: MCS_E_UNSUPPORTED (mcs_stitch_device).  Replaces, per capture,
  * StitcherBase.calibrate (:258-354) followed by StitcherBase.stitch (:211-256). */
 int mcs_stitch_direct(mcs_plan *plan, const uint8_t *const *d_cams,
                       const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
@@ -517,6 +520,11 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *job, double *H_io, int *ok_io, in
                                   int interp, uint8_t *const *d_out, int64_t out_pitch,
                                   int64_t out_capacity, void *stream, int *out_w, int *out_h,
                                   int *n_keypoints, int *n_matches, int *n_inliers);
+/* Blend mode of the per-capture plan that mcs_rig_job_wait_stitch[_batch] stitches with
+ * (mcs_plan_set_blend before its mcs_stitch_direct): MCS_BLEND_NONE (the default: the paste),
+ * MCS_BLEND_SEAM or MCS_BLEND_FEATHER; any other mode: MCS_E_INVALID.  Holds until changed; call
+ * it between captures, not while a wait_stitch of the job runs. */
+int mcs_rig_job_set_blend(mcs_rig_job *job, int mode);
 /* Captures the job finished on the device path (one launch chain) and on the per-call path (a
  * device ranking overflow, or MCS_RIG_PATH=calls). */
 int mcs_rig_job_counts(const mcs_rig_job *job, int *device_captures, int *call_captures);

@@ -54,6 +54,7 @@ EXPORTS = (
     "mcs_plan_set_lens", "mcs_lens_map_host", "mcs_plan_overlap_stats",
     "mcs_plan_overlap_stats_host", "mcs_gain_solve_host", "mcs_plan_set_gains", "mcs_plan_gains",
     "mcs_gain_apply_device", "mcs_stitch_device_gained", "mcs_stitch_direct_gained",
+    "mcs_rig_job_set_blend",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -264,6 +265,8 @@ def load() -> ctypes.CDLL:
         L.mcs_seam_graphcut_device.restype = I
         L.mcs_plan_seam_stats.argtypes = [P, P]
         L.mcs_plan_seam_stats.restype = I
+        L.mcs_rig_job_set_blend.argtypes = [P, I]
+        L.mcs_rig_job_set_blend.restype = I
         L.mcs_rig_job_counts.argtypes = [P, P, P]
         L.mcs_rig_job_counts.restype = I
         L.mcs_rig_job_destroy.argtypes = [P]
@@ -548,7 +551,8 @@ class Plan:
                       out_frame_stride: int, n_frames: int, stream: int = 0):
         """mcs_stitch_direct: the same pixels as stitch_device without prepared tables (the
         exact map evaluated per pixel in the kernel) -- for a plan built for one capture, e.g.
-        from per-frame homographies.  Paste / seam plans."""
+        from per-frame homographies.  Paste, seam and feather plans (feather: one pass over
+        the mosaic, mcs_direct_feather_*); multi-band needs stitch_device."""
         n = len(cam_ptrs)
         ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
         strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
@@ -1075,6 +1079,11 @@ class RigJob:
             self._kp.ctypes.data, self._m.ctypes.data, self._inl.ctypes.data))
         res = [((h[q], w[q]), self._stats(q)) for q in range(self.q)]
         return res[0] if self.q == 1 else res
+
+    def set_blend(self, mode: int):
+        """Blend mode of the capture's stitch in wait_stitch (mcs_rig_job_set_blend):
+        MCS_BLEND_NONE (the default), MCS_BLEND_SEAM or MCS_BLEND_FEATHER."""
+        check(self._lib.mcs_rig_job_set_blend(self._h, int(mode)))
 
     def counts(self):
         """(captures finished on the device path, on the per-call path)."""

@@ -519,9 +519,10 @@ static int stitch_direct_launch(mcs_plan *p, const uint8_t *const *d_cams,
     int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
                             n_frames, &kp);
     if (rc) return rc;
-    if (p->blend != MCS_BLEND_NONE && p->blend != MCS_BLEND_SEAM)
-        return mcs::fail(MCS_E_UNSUPPORTED, "mcs_stitch_direct renders paste / seam plans; "
-                         "blended plans need their prepared tables (mcs_stitch_device)");
+    if (p->blend != MCS_BLEND_NONE && p->blend != MCS_BLEND_SEAM && p->blend != MCS_BLEND_FEATHER)
+        return mcs::fail(MCS_E_UNSUPPORTED, "mcs_stitch_direct renders paste / seam / feather "
+                         "plans; multi-band plans need their prepared tables (mcs_stitch_device)");
+    const bool feather = p->blend == MCS_BLEND_FEATHER;
     gained = gained && gains_active(p);
     if (gained) fill_gain_q(p, &kp);
     if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames == 0) return MCS_OK;
@@ -560,9 +561,11 @@ static int stitch_direct_launch(mcs_plan *p, const uint8_t *const *d_cams,
         args.n_frames = uniform ? n_frames : 1;
         args.pad_ = 0;
         const unsigned fy = (unsigned)((args.n_frames + mcs::kDirectFrames - 1) / mcs::kDirectFrames);
-        rc = launch_args(A, (gained ? k->direct_g : k->direct)[p->fd.channels][p->fd.interp]
-                                                               [off32 ? 1 : 0],
-                         (unsigned)(gx * gy), fy, mcs::kWave, mcs::kWavesPerBlock, &args,
+        // (feather: the one-pass blend kernel over the same grid; it addresses frames by pointer)
+        const hipFunction_t fn =
+            feather ? (gained ? k->direct_feather_g : k->direct_feather)[p->fd.channels][p->fd.interp]
+                    : (gained ? k->direct_g : k->direct)[p->fd.channels][p->fd.interp][off32 ? 1 : 0];
+        rc = launch_args(A, fn, (unsigned)(gx * gy), fy, mcs::kWave, mcs::kWavesPerBlock, &args,
                          sizeof(args), s);
         if (rc) return rc;
     }

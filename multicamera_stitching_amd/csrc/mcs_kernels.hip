@@ -992,6 +992,146 @@ __device__ __forceinline__ void resize_px(const KResizeArgs &a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Direct feather (mcs_stitch_direct on a FEATHER plan): the feather rule of oracle/orc_blend.c
+// for every pixel of the mosaic in one pass, no prepared tables.  Tile grid and arguments of
+// direct_tile.  The slots run in the outer loop (wave-uniform: their parameters are scalar
+// loads), each pixel's map once per block of kDirectFrames captures; a slot no lane of the wave
+// is inside at positive distance costs its maps only.  Per capture and pixel the integer sums
+// sum d I per channel, one denominator sum d per pixel: no contributor list, no limit on the
+// slots a pixel mixes.
+//
+// Pass 1 (only waves that hold such a pixel): the pixels with D == 0 that a slot covers at
+// distance 0 (an image's outermost ring, nothing else at positive distance) take their owner's
+// sample -- blend_owner's rule restricted to distance 0: the lowest camera index (zkey: camera
+// << 8 | slot, the minimum), or the graph-cut label's camera when it covers the pixel (the last
+// such slot, as in blend_owner) -- written as the one-term sum with weight 1.
+
+// n / den for n >= 0, den >= 1, n / den < 2^8, r = rcp(den) to 1 ulp: the float estimate is off
+// by less than 2^-13, so its floor is within one of the quotient; one correction step.
+__device__ __forceinline__ uint32_t div_est(int n, int den, float r)
+{
+    int q = (int)((float)n * r);
+    const int rem = n - q * den;
+    q += (rem >= den ? 1 : 0) - (rem < 0 ? 1 : 0);
+    return (uint32_t)q;
+}
+
+template <int CN, int INTERP, bool GAIN = false>
+__device__ __forceinline__ void direct_feather_tile(const KParams &P, int n_frames)
+{
+    const int f0 = blockIdx.y * kDirectFrames;
+    const int nf = min(n_frames - f0, kDirectFrames);
+    const int gx = (P.out_w + kTileW - 1) / kTileW;
+    const int tile = (int)blockIdx.x;
+    int xg, y;
+    tile_pixel(tile % gx, tile / gx, threadIdx.x, threadIdx.y, xg, y);
+    if (xg >= P.out_w || y >= P.out_h) return;
+    const int npx = min(kPx, P.out_w - xg);
+    constexpr int kNoKey = 0x7fffffff;
+    int den[kPx], zkey[kPx], num[kDirectFrames][kPx * CN];
+#pragma unroll
+    for (int p = 0; p < kPx; p++) {
+        den[p] = 0;
+        zkey[p] = kNoKey;
+#pragma unroll
+        for (int f = 0; f < kDirectFrames; f++)
+#pragma unroll
+            for (int k = 0; k < CN; k++) num[f][p * CN + k] = 0;
+    }
+    uint32_t fix = 0, hset = 0;   // bit p: pixel p takes its distance-0 owner / has its label's
+    for (int pass = 0; pass < 2; pass++) {
+        if (pass) {
+#pragma unroll
+            for (int p = 0; p < kPx; p++)
+                fix |= (den[p] == 0 && zkey[p] != kNoKey) ? 1u << p : 0u;
+            if (__builtin_amdgcn_ballot_w64(fix != 0) == 0) break;
+        }
+        for (int s = 0; s <= P.n_stages; s++) {
+            int x32[kPx], y32[kPx], dd[kPx], cam = 0, w = 0, h = 0;
+            uint32_t sel = 0;
+#pragma unroll
+            for (int p = 0; p < kPx; p++) {
+                slot_xy<INTERP>(P, s, min(xg + p, P.out_w - 1), y, x32[p], y32[p], cam, w, h);
+                const int d = slot_dist(x32[p], y32[p], w, h);
+                bool take;
+                if (pass == 0) {
+                    if (d == 0) zkey[p] = min(zkey[p], (cam << 8) | s);
+                    take = d > 0;
+                    dd[p] = d;
+                } else {
+                    const bool hit = d == 0 && ((fix >> p) & 1u);
+                    // (the label read per slot: a rare pass, and four registers fewer held)
+                    const int hc = P.seam_hint
+                                       ? (int)P.seam_hint[(int64_t)(y >> P.seam_shift) * P.seam_w +
+                                                          (min(xg + p, P.out_w - 1) >> P.seam_shift)]
+                                       : (int)kBlendNone;
+                    const bool is_h = hit && cam == hc;
+                    take = is_h || (hit && (zkey[p] & 255) == s && !((hset >> p) & 1u));
+                    hset |= is_h ? 1u << p : 0u;
+                    dd[p] = 1;
+                }
+                sel |= take ? 1u << p : 0u;
+            }
+            if (__builtin_amdgcn_ballot_w64(sel != 0) == 0) continue;
+            const int64_t fstride = P.cam_fstride[cam];
+            const uint8_t *fb = P.cams[cam] + (int64_t)f0 * fstride;
+            const uint32_t q = GAIN ? gain_q_of(P, cam) : 256u;
+#pragma unroll
+            for (int p = 0; p < kPx; p++) {
+                if (!((sel >> p) & 1u)) continue;
+                if (pass) {
+                    den[p] = 0;
+#pragma unroll
+                    for (int f = 0; f < kDirectFrames; f++)
+#pragma unroll
+                        for (int k = 0; k < CN; k++) num[f][p * CN + k] = 0;
+                }
+                den[p] += dd[p];
+#pragma unroll
+                for (int f = 0; f < kDirectFrames; f++) {
+                    if (f >= nf) continue;
+                    const uint32_t v = sample_replicate<CN, GAIN>(fb + (int64_t)f * fstride, w, h,
+                                                                  x32[p], y32[p], q);
+#pragma unroll
+                    for (int k = 0; k < CN; k++)
+                        num[f][p * CN + k] += dd[p] * (int)((v >> (8 * k)) & 0xffu);
+                }
+            }
+        }
+    }
+    int dn[kPx];
+    float rc[kPx];
+#pragma unroll
+    for (int p = 0; p < kPx; p++) {
+        dn[p] = max(den[p], 1);   // (D == 0: the sums are 0 too, and 0 / 1 is the border value)
+        rc[p] = __builtin_amdgcn_rcpf((float)dn[p]);
+    }
+    uint8_t *dst = P.out + (int64_t)y * P.out_pitch + (int64_t)xg * CN;
+    const bool wide = npx == kPx && (((uintptr_t)dst | (uintptr_t)P.out_fstride) & 3) == 0;
+#pragma unroll
+    for (int f = 0; f < kDirectFrames; f++) {
+        if (f >= nf) continue;
+        OutWords wd;
+#pragma unroll
+        for (int p = 0; p < kPx; p++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int k = 0; k < CN; k++)
+                v |= div_est(num[f][p * CN + k] + den[p] / 2, dn[p], rc[p]) << (8 * k);
+            put_px<CN>(wd, p, v);
+        }
+        uint8_t *o = dst + (int64_t)(f0 + f) * P.out_fstride;
+        if (wide) {
+            uint32_t *o32 = reinterpret_cast<uint32_t *>(o);
+#pragma unroll
+            for (int i = 0; i < CN; i++) o32[i] = wd.at(i);
+        } else {
+            for (int b = 0; b < npx * CN; b++) o[b] = (uint8_t)(wd.at(b >> 2) >> (8 * (b & 3)));
+        }
+    }
+}
+
 }  // namespace mcs
 
 // ---------------------------------------------------------------------------------------------
@@ -1272,3 +1412,21 @@ MCS_FEATHER_ENTRY(3, 0, _g, true)
 MCS_FEATHER_ENTRY(3, 1, _g, true)
 MCS_FEATHER_ENTRY(4, 0, _g, true)
 MCS_FEATHER_ENTRY(4, 1, _g, true)
+
+// Direct feather (mcs_stitch_direct / _gained on a FEATHER plan): block (64, 8, 1) over every
+// tile, grid y over blocks of kDirectFrames captures; KDirectArgs (fallback unused, NULL).
+#define MCS_DIRECT_FEATHER_ENTRY(CN, IN, GS, GAIN)                                             \
+    extern "C" __global__ __launch_bounds__(512) void mcs_direct_feather_c##CN##_i##IN##GS(    \
+        const mcs::KParams P, const int *fallback, int n_frames)                               \
+    {                                                                                          \
+        mcs::direct_feather_tile<CN, IN, GAIN>(P, n_frames);                                   \
+    }
+#define MCS_DIRECT_FEATHER_ENTRIES(CN)                                                         \
+    MCS_DIRECT_FEATHER_ENTRY(CN, 0, , false)                                                   \
+    MCS_DIRECT_FEATHER_ENTRY(CN, 1, , false)                                                   \
+    MCS_DIRECT_FEATHER_ENTRY(CN, 0, _g, true)                                                  \
+    MCS_DIRECT_FEATHER_ENTRY(CN, 1, _g, true)
+MCS_DIRECT_FEATHER_ENTRIES(1)
+MCS_DIRECT_FEATHER_ENTRIES(2)
+MCS_DIRECT_FEATHER_ENTRIES(3)
+MCS_DIRECT_FEATHER_ENTRIES(4)

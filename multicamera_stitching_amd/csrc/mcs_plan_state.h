@@ -197,6 +197,9 @@ struct Kernels {
     hipFunction_t feather_g[5][2] = {};
     hipFunction_t mb_levels_g[5] = {};
     hipFunction_t mb_bands_g[5][2][3] = {};
+    // direct feather (mcs_stitch_direct on a FEATHER plan): [channels][interp], and its _g twins
+    hipFunction_t direct_feather[5][2] = {};
+    hipFunction_t direct_feather_g[5][2] = {};
 };
 
 // mcs_prepare.cpp

@@ -81,6 +81,10 @@ int kernels(const Api *A, int device, const Kernels **out)
                 if (rc == MCS_OK) rc = fn(name, &k.mb_bdesc[c][i]);
                 snprintf(name, sizeof(name), "mcs_seam_sample_c%d_i%d", c, i);
                 if (rc == MCS_OK) rc = fn(name, &k.seam_sample[c][i]);
+                snprintf(name, sizeof(name), "mcs_direct_feather_c%d_i%d", c, i);
+                if (rc == MCS_OK) rc = fn(name, &k.direct_feather[c][i]);
+                snprintf(name, sizeof(name), "mcs_direct_feather_c%d_i%d_g", c, i);
+                if (rc == MCS_OK) rc = fn(name, &k.direct_feather_g[c][i]);
                 for (int o = 0; o < 2 && rc == MCS_OK; o++) {
                     snprintf(name, sizeof(name), "mcs_direct_c%d_i%d_o%d", c, i, o ? 32 : 64);
                     rc = fn(name, &k.direct[c][i][o]);

@@ -146,6 +146,8 @@ struct mcs_rig_job {
     bool busy = false, done = true;
     RigDevice dev;
     int captures_device = 0, captures_calls = 0;   // captures finished by each path
+    // blend mode of the per-capture plan of wait_stitch (mcs_rig_job_set_blend)
+    int blend = MCS_BLEND_NONE;
 };
 
 namespace {
@@ -713,7 +715,8 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         rc = mcs_plan_create(st, np, j->w, j->h, j->channels, interp, j->device, &plan);
         if (rc) return rc;
         int w = 0, h = 0, c = 0;
-        rc = mcs_plan_out_shape(plan, &w, &h, &c);
+        if (j->blend != MCS_BLEND_NONE) rc = mcs_plan_set_blend(plan, j->blend);
+        if (rc == MCS_OK) rc = mcs_plan_out_shape(plan, &w, &h, &c);
         if (rc == MCS_OK && ((int64_t)w * c > out_pitch || (int64_t)h * out_pitch > out_capacity))
             rc = mcs::fail(MCS_E_SHAPE, "mosaic %d x %d does not fit the output (pitch %lld, "
                            "%lld bytes)", w, h, (long long)out_pitch, (long long)out_capacity);
@@ -744,6 +747,17 @@ int mcs_rig_job_wait_stitch(mcs_rig_job *j, double *H_io, int *ok_io, int super_
     return mcs_rig_job_wait_stitch_batch(j, H_io, ok_io, super_mode, interp, &d_out, out_pitch,
                                          out_capacity, stream, out_w, out_h, n_keypoints,
                                          n_matches, n_inliers);
+}
+
+int mcs_rig_job_set_blend(mcs_rig_job *j, int mode)
+{
+    mcs::clear_error();
+    if (!j) return mcs::fail(MCS_E_INVALID, "NULL job");
+    if (mode != MCS_BLEND_NONE && mode != MCS_BLEND_SEAM && mode != MCS_BLEND_FEATHER)
+        return mcs::fail(MCS_E_INVALID, "blend mode %d: a rig job stitches with the direct path "
+                         "(NONE, SEAM or FEATHER)", mode);
+    j->blend = mode;
+    return MCS_OK;
 }
 
 int mcs_rig_job_counts(const mcs_rig_job *j, int *device_captures, int *call_captures)

@@ -155,8 +155,13 @@ class CaptureEstimator:
                  fast_threshold: int = 20, ratio: float = 0.75, reproj_thresh: float = 3.0,
                  iters: int = 2000, seed: int = 0, super_mode: bool = False,
                  interp: int = _capi.MCS_INTER_LINEAR, device: int = 0, threads: int = None,
-                 captures_per_job: int = 1):
+                 captures_per_job: int = 1, blend: int = _capi.MCS_BLEND_NONE):
         self.n_cams, self.w, self.h, self.c = n_cams, width, height, channels
+        # blend mode of the capture's direct stitch (stitch / collect_stitch): NONE (the paste),
+        # SEAM or FEATHER
+        if blend not in (_capi.MCS_BLEND_NONE, _capi.MCS_BLEND_SEAM, _capi.MCS_BLEND_FEATHER):
+            raise ValueError(f"blend mode {blend}: the direct stitch renders NONE, SEAM or FEATHER")
+        self.blend = blend
         # rig jobs of several captures (mcs_rig_job_create_batch: one launch chain over all their
         # cameras; submit / collect_stitch then take that many captures at once)
         self.batch = captures_per_job
@@ -189,6 +194,8 @@ class CaptureEstimator:
             self._jobs[slot] = _capi.RigJob(self.n_cams, self.w, self.h, self.c, nf, nl, sf, ft,
                                             self.ratio, self.thresh, self.iters, self.seed,
                                             self.device, captures=self.batch)
+            if self.blend != _capi.MCS_BLEND_NONE:
+                self._jobs[slot].set_blend(self.blend)
         return self._jobs[slot]
 
     def submit(self, frame_ptrs, wait_event: int = 0, slot: int = 0):
@@ -311,6 +318,8 @@ class CaptureEstimator:
         """Stitch one capture with its homographies into out (rows out_pitch bytes apart,
         out_capacity bytes).  Returns the plan (its out_w / out_h give the mosaic's size)."""
         plan, _ = self.plan(pair_H)
+        if self.blend != _capi.MCS_BLEND_NONE:
+            plan.set_blend(self.blend)
         if plan.out_w * self.c > out_pitch or plan.out_h * out_pitch > out_capacity:
             plan.close()
             raise ValueError(f"mosaic {plan.out_w} x {plan.out_h} does not fit the output buffer")

@@ -93,6 +93,18 @@ def estimate_cpu(frames, args):
     return out
 
 
+# --blend: the direct stitch's mode (_capi.MCS_BLEND_*) and its name in the printed line
+BLENDS = {"none": 0, "seam": 3, "feather": 1}
+BLEND_NAMES = {"none": "paste", "seam": "seam", "feather": "feather"}
+
+
+def cpu_render(oracle, plan, frames, blend):
+    """The CPU restatement of the mosaic the capture's stitch rendered."""
+    if blend == "none":
+        return oracle.flat_stitch(plan.describe(), frames)
+    return oracle.blend_stitch(plan.describe(), frames, BLENDS[blend])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
@@ -125,6 +137,9 @@ def main():
     ap.add_argument("--stitch-streams", action="store_true",
                     help="pipelined: each slot's stitches on a stream of their own (default: one "
                          "stitch stream)")
+    ap.add_argument("--blend", choices=("none", "seam", "feather"), default="none",
+                    help="with --stitch: blend mode of the capture's direct stitch (none: the "
+                         "paste; seam; feather: mcs_direct_feather_*)")
     ap.add_argument("--pinned", action="store_true",
                     help="camera frames in pinned host buffers (default: pageable numpy arrays, "
                          "as the reference's capture loop holds them)")
@@ -199,7 +214,8 @@ def stitch_main(args, frames, truth, W, Hh, N):
     d = [torch.empty(f.shape, dtype=torch.uint8, device=dev) for f in frames]
     pitch = 8192 * 3
     out = torch.empty((2048, pitch), dtype=torch.uint8, device=dev)
-    est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads)
+    est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
+                                    blend=BLENDS[args.blend])
     ptrs = [t.data_ptr() for t in d]
     tot = {"upload": 0.0, "estimate": 0.0, "plan_stitch": 0.0}
     mpix = 0.0
@@ -232,7 +248,7 @@ def stitch_main(args, frames, truth, W, Hh, N):
     pair_H, plan = capture(False)
     ow, oh = plan.out_w, plan.out_h
     got = out[:oh, :ow * 3].cpu().numpy().reshape(oh, ow, 3)
-    want = oracle.flat_stitch(plan.describe(), frames)
+    want = cpu_render(oracle, plan, frames, args.blend)
     plan.close()
     est.close()
     errs = [pair_error(h, T, W, Hh) if h is not None else None for h, T in zip(pair_H, truth)]
@@ -247,7 +263,8 @@ def stitch_main(args, frames, truth, W, Hh, N):
         "config": {"workload": "BASELINE configs[2] + per-capture stitch: ORB nfeatures %d, 8 "
                                "levels x 1.2, FAST 20; Hamming kNN-2, ratio 0.75; RANSAC 3.0 px, "
                                "2000 hypotheses + LM; chain geometry + plan on the host "
-                               "(in Python); mcs_stitch_direct (paste)" % args.nfeatures,
+                               "(in Python); mcs_stitch_direct (%s)" % (
+                                   args.nfeatures, BLEND_NAMES[args.blend]),
                    "host_frames": "pageable, uploaded every capture",
                    "host_threads": args.threads},
         "stage_ms_per_capture": {k: round(v / args.steps * 1e3, 3) for k, v in tot.items()},
@@ -297,7 +314,7 @@ def pipelined_main(args, frames, truth, W, Hh, N):
     for e in ev_done:
         e.record(sts[0])
     est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
-                                    captures_per_job=B)
+                                    captures_per_job=B, blend=BLENDS[args.blend])
     pending = [None] * D          # plan of the capture last stitched from frame set / output i
     lat = []
 
@@ -392,7 +409,7 @@ def pipelined_main(args, frames, truth, W, Hh, N):
             link = reps * sum(h.numel() for h in host) / (time.perf_counter() - tl) / 1e9
     ow, oh = plan.out_w, plan.out_h
     got = out[slot][:oh, :ow * 3].cpu().numpy().reshape(oh, ow, 3)
-    want = oracle.flat_stitch(plan.describe(), frames)
+    want = cpu_render(oracle, plan, frames, args.blend)
     for q in pending:
         if q is not None:
             q.close()
@@ -409,9 +426,9 @@ def pipelined_main(args, frames, truth, W, Hh, N):
         "config": {"workload": "BASELINE configs[2] + per-capture stitch: ORB nfeatures %d, 8 "
                                "levels x 1.2, FAST 20; Hamming kNN-2, ratio 0.75; RANSAC 3.0 px, "
                                "2000 hypotheses + LM; chain geometry + plan on the host "
-                               "(%s); mcs_stitch_direct (paste)" % (
+                               "(%s); mcs_stitch_direct (%s)" % (
                                    args.nfeatures, "in libmcs: mcs_rig_job_wait_stitch"
-                                   if lib_stitch else "in Python"),
+                                   if lib_stitch else "in Python", BLEND_NAMES[args.blend]),
                    "host_frames": "pinned, uploaded every capture on their own stream while the "
                                   "previous captures are estimated and stitched",
                    "pipeline_depth": D, "rig_jobs": bool(args.overlap),
