@@ -301,6 +301,26 @@ int mcs_plan_overlap_stats(mcs_plan *plan, const uint8_t *const *d_cams,
 /* The same for one capture of host frames (sorted-label order, calibrated sizes). */
 int mcs_plan_overlap_stats_host(mcs_plan *plan, const uint8_t *const *cams, int step_log2,
                                 int64_t *N, int64_t *S);
+/* The same N and S without the table, for a plan that lives for one capture (per-capture
+ * homographies): one kernel (mcs_direct_overlap_*) evaluates every grid point's positions,
+ * coverage and luminances and adds them up; nothing is stored per point and the plan keeps no
+ * device state of it.  Arguments, checks, outputs and error codes as mcs_plan_overlap_stats; the
+ * results are equal, bit for bit.  A table the plan has (from mcs_plan_overlap_stats) is neither
+ * used nor dropped.  No size limit: step_log2 = 0 works for every mosaic.  One memset, one launch
+ * (any frame strides), one copy back and one synchronise of `stream` (NULL: the plan's own).  The
+ * accumulators are a small device buffer of the calling thread, grown on demand and kept. */
+int mcs_plan_overlap_stats_direct(mcs_plan *plan, const uint8_t *const *d_cams,
+                                  const int64_t *cam_frame_stride, int n_frames, int step_log2,
+                                  int64_t *N, int64_t *S, void *stream);
+/* The same launch, enqueued only: d_stats is a device buffer of the caller, (1 + n_frames) x
+ * n_cams^2 int64 -- N, then S --, zeroed by the call on `stream` and filled by the kernel.  No
+ * synchronisation, and for a chain plan without lenses no allocation: its geometry travels in the
+ * kernel arguments, so the plan may be destroyed right after the call, as with mcs_stitch_direct.
+ * (A cylindrical or lensed plan uploads its device tables on first use, as every launch of it.)
+ * `stream` NULL: the device's default stream.  An empty mosaic: d_stats zeroed, no launch. */
+int mcs_plan_overlap_stats_direct_async(mcs_plan *plan, const uint8_t *const *d_cams,
+                                        const int64_t *cam_frame_stride, int n_frames,
+                                        int step_log2, int64_t *d_stats, void *stream);
 /* Gains from the statistics of ONE capture (host FP64, no device): the minimiser of Brown &
  * Lowe's objective as detail::GainCompensator builds it.  With I_ij = S_ij / (channels N_ij) (0
  * where N_ij = 0): for every i, j: b_i += beta N_ij, A_ii += beta N_ij; for j != i also
@@ -498,7 +518,13 @@ int mcs_rig_job_wait(mcs_rig_job *job, double *H, int *ok, int *n_keypoints, int
  * and mcs_stitch_direct of the submitted frames into d_out (rows out_pitch bytes apart, at most
  * out_capacity bytes) on `stream` (enqueued; the frames and d_out must stay valid until it has
  * run).  out_w / out_h: the mosaic's size.  Replaces estimate.CaptureEstimator.collect + stitch
- * (chain geometry and plan built per capture in Python). */
+ * (chain geometry and plan built per capture in Python).  With exposure enabled
+ * (mcs_rig_job_set_exposure) the capture's stitch is "estimate, compensate, stitch": per capture
+ * mcs_plan_overlap_stats_direct_async of its plan and frames on `stream`, then -- for all
+ * captures of the call together -- one copy of the statistics to the host and ONE synchronise of
+ * `stream` before any stitch is enqueued, then per capture mcs_gain_solve_host,
+ * mcs_plan_set_gains and mcs_stitch_direct_gained.  Without it the call never synchronises
+ * `stream`. */
 int mcs_rig_job_wait_stitch(mcs_rig_job *job, double *H_io, int *ok_io, int super_mode,
                             int interp, uint8_t *d_out, int64_t out_pitch, int64_t out_capacity,
                             void *stream, int *out_w, int *out_h, int *n_keypoints,
@@ -525,6 +551,20 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *job, double *H_io, int *ok_io, in
  * MCS_BLEND_SEAM or MCS_BLEND_FEATHER; any other mode: MCS_E_INVALID.  Holds until changed; call
  * it between captures, not while a wait_stitch of the job runs. */
 int mcs_rig_job_set_blend(mcs_rig_job *job, int mode);
+/* Per-capture exposure gains of mcs_rig_job_wait_stitch[_batch] (see there): step_log2 0..4
+ * enables them on that grid step, a negative step_log2 disables them (the default: the calls
+ * launch exactly what they launch without this entry point); any other step: MCS_E_INVALID.
+ * alpha, beta: mcs_gain_solve_host's; <= 0 selects OpenCV's 0.01 and 100; not finite:
+ * MCS_E_INVALID.  A camera the mosaic does not use (uncalibrated from a failed pair on) has
+ * N_ii = 0 and keeps gain 1.  The job owns the statistics' device and pinned host buffers
+ * (allocated on first use).  Holds until changed; the calling rule of mcs_rig_job_set_blend. */
+int mcs_rig_job_set_exposure(mcs_rig_job *job, int step_log2, double alpha, double beta);
+/* The gains of the last mcs_rig_job_wait_stitch[_batch]: gains (n_captures x n_cams doubles, the
+ * solver's) and q (as many uint16, what the kernels applied: mcs_plan_set_gains' quantisation);
+ * enabled: whether exposure is enabled.  Before the first such call, or with exposure disabled:
+ * 1.0 and 256.  Any pointer may be NULL.  No temporal smoothing is done: a caller that wants it
+ * has the values here. */
+int mcs_rig_job_gains(const mcs_rig_job *job, double *gains, uint16_t *q, int *enabled);
 /* Captures the job finished on the device path (one launch chain) and on the per-call path (a
  * device ranking overflow, or MCS_RIG_PATH=calls). */
 int mcs_rig_job_counts(const mcs_rig_job *job, int *device_captures, int *call_captures);

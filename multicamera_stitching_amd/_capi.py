@@ -54,7 +54,8 @@ EXPORTS = (
     "mcs_plan_set_lens", "mcs_lens_map_host", "mcs_plan_overlap_stats",
     "mcs_plan_overlap_stats_host", "mcs_gain_solve_host", "mcs_plan_set_gains", "mcs_plan_gains",
     "mcs_gain_apply_device", "mcs_stitch_device_gained", "mcs_stitch_direct_gained",
-    "mcs_rig_job_set_blend",
+    "mcs_rig_job_set_blend", "mcs_plan_overlap_stats_direct",
+    "mcs_plan_overlap_stats_direct_async", "mcs_rig_job_set_exposure", "mcs_rig_job_gains",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -329,6 +330,15 @@ def load() -> ctypes.CDLL:
         L.mcs_plan_overlap_stats.argtypes = [P, ctypes.POINTER(P), ctypes.POINTER(i64), I, I, P, P,
                                              P]
         L.mcs_plan_overlap_stats.restype = I
+        L.mcs_plan_overlap_stats_direct.argtypes = L.mcs_plan_overlap_stats.argtypes
+        L.mcs_plan_overlap_stats_direct.restype = I
+        L.mcs_plan_overlap_stats_direct_async.argtypes = [P, ctypes.POINTER(P),
+                                                          ctypes.POINTER(i64), I, I, P, P]
+        L.mcs_plan_overlap_stats_direct_async.restype = I
+        L.mcs_rig_job_set_exposure.argtypes = [P, I, ctypes.c_double, ctypes.c_double]
+        L.mcs_rig_job_set_exposure.restype = I
+        L.mcs_rig_job_gains.argtypes = [P, P, P, ctypes.POINTER(I)]
+        L.mcs_rig_job_gains.restype = I
         L.mcs_plan_overlap_stats_host.argtypes = [P, ctypes.POINTER(P), I, P, P]
         L.mcs_plan_overlap_stats_host.restype = I
         L.mcs_gain_solve_host.argtypes = [I, P, P, I, ctypes.c_double, ctypes.c_double, P]
@@ -649,6 +659,31 @@ class Plan:
                                                int(step_log2), N.ctypes.data, S.ctypes.data,
                                                ctypes.c_void_p(int(stream))))
         return N, S
+
+    def overlap_stats_direct(self, cam_ptrs, cam_frame_strides, n_frames: int, step_log2: int = 2,
+                             stream: int = 0):
+        """mcs_plan_overlap_stats_direct: overlap_stats' (N, S) from one table-free launch (for
+        a plan that lives for one capture; no size limit at step_log2 = 0)."""
+        n = self.n_cams
+        ptrs = (ctypes.c_void_p * n)(*[int(p) if p else None for p in cam_ptrs])
+        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
+        N = np.zeros((n, n), np.int64)
+        S = np.zeros((max(int(n_frames), 0), n, n), np.int64)
+        check(self._lib.mcs_plan_overlap_stats_direct(self._h, ptrs, strides, int(n_frames),
+                                                      int(step_log2), N.ctypes.data, S.ctypes.data,
+                                                      ctypes.c_void_p(int(stream))))
+        return N, S
+
+    def overlap_stats_direct_async(self, cam_ptrs, cam_frame_strides, n_frames: int,
+                                   step_log2: int, stats_ptr: int, stream: int = 0):
+        """mcs_plan_overlap_stats_direct_async: the same launch, enqueued only, into the device
+        buffer stats_ptr ((1 + n_frames) * n_cams^2 int64: N, then S; zeroed by the call)."""
+        n = self.n_cams
+        ptrs = (ctypes.c_void_p * n)(*[int(p) if p else None for p in cam_ptrs])
+        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
+        check(self._lib.mcs_plan_overlap_stats_direct_async(
+            self._h, ptrs, strides, int(n_frames), int(step_log2),
+            ctypes.c_void_p(int(stats_ptr)), ctypes.c_void_p(int(stream))))
 
     def overlap_stats_host(self, cams, step_log2: int = 2):
         """mcs_plan_overlap_stats_host: one capture of host frames (sorted-label order,
@@ -1084,6 +1119,25 @@ class RigJob:
         """Blend mode of the capture's stitch in wait_stitch (mcs_rig_job_set_blend):
         MCS_BLEND_NONE (the default), MCS_BLEND_SEAM or MCS_BLEND_FEATHER."""
         check(self._lib.mcs_rig_job_set_blend(self._h, int(mode)))
+
+    def set_exposure(self, step_log2: int, alpha: float = 0.0, beta: float = 0.0):
+        """Per-capture exposure gains in wait_stitch (mcs_rig_job_set_exposure): statistics on
+        the 2^step_log2 grid (0..4), solved and fused into the capture's stitch; a negative
+        step_log2 disables them (the default).  alpha, beta <= 0: OpenCV's 0.01 and 100."""
+        check(self._lib.mcs_rig_job_set_exposure(self._h, int(step_log2), float(alpha),
+                                                 float(beta)))
+
+    def gains(self):
+        """(gains, q, enabled) of the last wait_stitch (mcs_rig_job_gains): float64 and uint16
+        arrays of shape (n_cams,), or (captures, n_cams) for a batch job; 1.0 and 256 before the
+        first one or with exposure disabled."""
+        g = np.ones(self.q * self.n, np.float64)
+        q = np.full(self.q * self.n, 256, np.uint16)
+        on = ctypes.c_int(0)
+        check(self._lib.mcs_rig_job_gains(self._h, g.ctypes.data, q.ctypes.data, ctypes.byref(on)))
+        if self.q > 1:
+            g, q = g.reshape(self.q, self.n), q.reshape(self.q, self.n)
+        return g, q, bool(on.value)
 
     def counts(self):
         """(captures finished on the device path, on the per-call path)."""

@@ -1,8 +1,9 @@
 // mcs_gain.cpp -- exposure gain compensation (include/mcs.h "Exposure"): the overlap statistics
 // of a plan (table built once per plan and grid step, sums per batch of captures), the gain solve
 // (host FP64, Brown & Lowe's objective as OpenCV's detail::GainCompensator states it), the gains a
-// plan carries and the kernel that applies one to a camera's source bytes.  Device code:
-// mcs_gain.h.
+// plan carries and the kernel that applies one to a camera's source bytes; and the table-free
+// statistics of a plan that lives for one capture (mcs_plan_overlap_stats_direct[_async]: one
+// launch, nothing kept on the plan).  Device code: mcs_gain.h.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -117,6 +118,68 @@ int build_overlap(const Api *A, mcs_plan *p, const Kernels *kn, int k, hipStream
             ov.N[i * MCS_MAX_CAMS + j] = ov.N[j * MCS_MAX_CAMS + i] = cnt[i * MCS_MAX_CAMS + j];
     return MCS_OK;
 }
+
+// The argument checks of the direct entry points after their NULL checks: those of
+// mcs_plan_overlap_stats, in its order.
+int check_stats_args(const mcs_plan *p, const uint8_t *const *d_cams, int n_frames, int step_log2)
+{
+    if (p->single)
+        return mcs::fail(MCS_E_UNSUPPORTED, "a single-camera remap plan (warp / undistort) has "
+                         "no overlaps");
+    if (step_log2 < 0 || step_log2 > 4)
+        return mcs::fail(MCS_E_INVALID, "step_log2 %d (0..4)", step_log2);
+    if (n_frames < 1 || n_frames > 65535) return mcs::fail(MCS_E_INVALID, "n_frames=%d", n_frames);
+    bool need[MCS_MAX_CAMS];
+    need_mask(p->fd, need);
+    for (int i = 0; i < p->fd.n_cams; i++)
+        if (need[i] && !d_cams[i]) return mcs::fail(MCS_E_INVALID, "d_cams[%d] NULL", i);
+    return MCS_OK;
+}
+
+// The table-free statistics of checked arguments on stream s (the device is set): d_stats zeroed,
+// then one launch of mcs_direct_overlap_* unless the mosaic is empty.
+int enqueue_direct_stats(const Api *A, mcs_plan *p, const uint8_t *const *d_cams,
+                         const int64_t *cam_frame_stride, int n_frames, int k,
+                         unsigned long long *d_stats, hipStream_t s)
+{
+    const int n = p->fd.n_cams, C = p->fd.channels;
+    const size_t bytes = (size_t)(1 + n_frames) * n * n * sizeof(unsigned long long);
+    HIP_TRY(A->hipMemsetAsync(d_stats, 0, bytes, s));
+    if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
+    const Kernels *kn = nullptr;
+    int rc = kernels(A, p->device, &kn);
+    if (rc) return rc;
+    rc = upload_plan_tables(A, p, s);   // (cylinder / lensed plans: their device tables, once)
+    if (rc) return rc;
+    mcs::KDirectOverlapArgs a;
+    memset(&a, 0, sizeof(a));
+    a.P = p->kp;
+    for (int i = 0; i < n; i++) {
+        a.P.cams[i] = d_cams[i];
+        a.P.cam_fstride[i] = cam_frame_stride ? cam_frame_stride[i]
+                                              : (int64_t)p->fd.cam_w[i] * p->fd.cam_h[i] * C;
+    }
+    a.P.out = nullptr;
+    a.stats = d_stats;
+    a.gw = (p->fd.out_w + (1 << k) - 1) >> k;
+    a.gh = (p->fd.out_h + (1 << k) - 1) >> k;
+    a.k = k;
+    a.n_frames = n_frames;
+    a.n_cams = n;
+    return launch_args(A, kn->direct_overlap[C][p->fd.interp],
+                       mcs::dov_blocks((int64_t)a.gw * a.gh),
+                       (unsigned)((n_frames + mcs::kOvFrames - 1) / mcs::kOvFrames),
+                       mcs::kDovThreads, 1, &a, sizeof(a), s);
+}
+
+// The accumulators of mcs_plan_overlap_stats_direct: per calling thread and device, grown on
+// demand, kept for the thread's next call (the call synchronises before it returns, so the
+// buffer is idle between calls; it is never freed).
+struct StatsScratch {
+    unsigned long long *d = nullptr;
+    size_t bytes = 0;
+};
+thread_local StatsScratch tl_stats[mcs::kMaxDevices];
 
 }  // namespace
 
@@ -364,6 +427,72 @@ int mcs_plan_overlap_stats(mcs_plan *p, const uint8_t *const *d_cams,
     if (rc) return rc;
     HIP_TRY(A->hipMemcpyAsync(S, ov.d_S, s_bytes, hipMemcpyDeviceToHost, s));
     HIP_TRY(A->hipStreamSynchronize(s));
+    return MCS_OK;
+}
+
+int mcs_plan_overlap_stats_direct_async(mcs_plan *p, const uint8_t *const *d_cams,
+                                        const int64_t *cam_frame_stride, int n_frames,
+                                        int step_log2, int64_t *d_stats, void *stream)
+{
+    mcs::clear_error();
+    if (!p || !d_cams || !d_stats) return mcs::fail(MCS_E_INVALID, "NULL plan/d_cams/d_stats");
+    const int rc = check_stats_args(p, d_cams, n_frames, step_log2);
+    if (rc) return rc;
+    const Api *A = mcs::rt::api();
+    if (!A) return MCS_E_HIP;
+    DeviceGuard g(A, p->device);
+    if (g.err != hipSuccess)
+        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    return enqueue_direct_stats(A, p, d_cams, cam_frame_stride, n_frames, step_log2,
+                                reinterpret_cast<unsigned long long *>(d_stats),
+                                (hipStream_t)stream);
+}
+
+int mcs_plan_overlap_stats_direct(mcs_plan *p, const uint8_t *const *d_cams,
+                                  const int64_t *cam_frame_stride, int n_frames, int step_log2,
+                                  int64_t *N, int64_t *S, void *stream)
+{
+    mcs::clear_error();
+    if (!p || !d_cams || !N || !S) return mcs::fail(MCS_E_INVALID, "NULL plan/d_cams/N/S");
+    int rc = check_stats_args(p, d_cams, n_frames, step_log2);
+    if (rc) return rc;
+    const int n = p->fd.n_cams;
+    const size_t nn = (size_t)n * n, count = (1 + (size_t)n_frames) * nn;
+    for (size_t i = 0; i < nn; i++) N[i] = 0;
+    for (size_t i = 0; i < count - nn; i++) S[i] = 0;
+    if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
+    const Api *A = mcs::rt::api();
+    if (!A) return MCS_E_HIP;
+    DeviceGuard g(A, p->device);
+    if (g.err != hipSuccess)
+        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    hipStream_t s = (hipStream_t)stream;
+    if (!s) {
+        rc = ensure_stream(A, p);
+        if (rc) return rc;
+        s = p->stream;
+    }
+    StatsScratch &sc = tl_stats[p->device];
+    const size_t bytes = count * sizeof(unsigned long long);
+    if (sc.bytes < bytes) {
+        if (sc.d) HIP_TRY(A->hipFree(sc.d));
+        sc.d = nullptr;
+        sc.bytes = 0;
+        HIP_TRY(A->hipMalloc((void **)&sc.d, bytes));
+        sc.bytes = bytes;
+    }
+    rc = enqueue_direct_stats(A, p, d_cams, cam_frame_stride, n_frames, step_log2, sc.d, s);
+    static thread_local std::vector<int64_t> host;
+    host.resize(count);
+    hipError_t e = hipSuccess;
+    if (rc == MCS_OK) e = A->hipMemcpyAsync(host.data(), sc.d, bytes, hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = A->hipStreamSynchronize(s);   // (drains the queued work on error too)
+    if (rc) return rc;
+    if (e != hipSuccess || e2 != hipSuccess)
+        return mcs::fail(MCS_E_HIP, "overlap statistics: %s",
+                         A->hipGetErrorString(e != hipSuccess ? e : e2));
+    memcpy(N, host.data(), nn * sizeof(int64_t));
+    memcpy(S, host.data() + nn, (count - nn) * sizeof(int64_t));
     return MCS_OK;
 }
 

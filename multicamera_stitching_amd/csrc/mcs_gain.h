@@ -1,6 +1,8 @@
 // mcs_gain.h -- device code of exposure gain compensation, included by mcs_kernels.hip after
 // mcs_blend.h (one code object): the overlap table of a plan (prepare once per plan and grid
-// step), the per-capture overlap sums over it, and the per-camera gain on source bytes.
+// step), the per-capture overlap sums over it, the same statistics without a table (one launch
+// per batch of captures, for a plan that lives for one capture), and the per-camera gain on
+// source bytes.
 //
 // The statistics use the blend's own geometry: a camera slot's position at a grid point is
 // slot_xy's, it covers the point iff slot_dist >= 0, and its luminance there is the sum of the
@@ -140,6 +142,107 @@ __device__ __forceinline__ void overlap_sum(const KOverlapSumArgs &a)
     // S[f][i][j]: camera i's luminance over the points of pair (i, j)
     const int i = dir ? u.cam_b : u.cam_a, j = dir ? u.cam_a : u.cam_b;
     atomicAdd(&a.S[((int64_t)(f0 + f) * a.n_cams + i) * a.n_cams + j], (unsigned long long)s);
+}
+
+// ---- table-free statistics (mcs_plan_overlap_stats_direct) ------------------------------------
+// The N and S of the two kernels above in one launch, nothing stored: grid (dov_blocks(points),
+// ceil(n_frames / kOvFrames)), block kDovThreads.  A block strides over the grid points, one lane
+// per point.  Per point: the covering slots (slot_xy + slot_dist of every slot), then per slot s
+// that some lane of the wave covers its luminance in up to kOvFrames captures (two captures per
+// dword, 16 bits each) and, for every slot t of another camera -- and t = s, the diagonal --, the
+// wave's lanes covered by both: N[cam_s][cam_t] gets their number, S[f][cam_s][cam_t] the sum of
+// their luminances (the ordered pairs (s, t) and (t, s) give overlap_prep's two directions).  The
+// wave's sums go to the block's 32-bit LDS partials (one ds_add per wave, pair and dword), the
+// block's non-zero partials to the 64-bit accumulators at the end.  Blocks of grid row 0 count N.
+template <int CN, int INTERP>
+__device__ __forceinline__ void direct_overlap(const KDirectOverlapArgs &a)
+{
+    const KParams &P = a.P;
+    __shared__ uint32_t part_n[kOvSegs];
+    __shared__ uint32_t part_s[kOvFrames][kOvSegs];
+    const int tid = threadIdx.x, lane = tid & (kWave - 1);
+    part_n[tid] = 0;
+#pragma unroll
+    for (int f = 0; f < kOvFrames; f++) part_s[f][tid] = 0;
+    __syncthreads();
+    const int f0 = blockIdx.y * kOvFrames;
+    const int nf = min(kOvFrames, a.n_frames - f0);
+    const bool count = blockIdx.y == 0;
+    const int64_t np = (int64_t)a.gw * a.gh;
+    // the block's first point of each round, as (column, row) of the grid: advanced without a
+    // division (the step is one division away, once)
+    const int64_t step = (int64_t)gridDim.x * kDovThreads;
+    const int step_x = (int)(step % a.gw), step_y = (int)(step / a.gw);
+    int64_t base = (int64_t)blockIdx.x * kDovThreads;
+    int bx = (int)(base % a.gw), by = (int)(base / a.gw);
+    for (; base < np; base += step) {
+        const bool live = base + tid < np;
+        const uint32_t t0 = (uint32_t)(bx + tid);
+        const int x = live ? (int)(t0 % (uint32_t)a.gw) << a.k : 0;
+        const int y = live ? (by + (int)(t0 / (uint32_t)a.gw)) << a.k : 0;
+        bx += step_x;
+        by += step_y;
+        if (bx >= a.gw) bx -= a.gw, by++;
+        uint32_t cov = 0;
+        if (live) {
+            for (int s = 0; s <= P.n_stages; s++) {
+                int x32, y32, cam, w, h;
+                slot_xy<INTERP>(P, s, x, y, x32, y32, cam, w, h);
+                if (slot_dist(x32, y32, w, h) >= 0) cov |= 1u << s;
+            }
+        }
+        for (int s = 0; s <= P.n_stages; s++) {
+            const bool in_s = (cov >> s) & 1u;
+            if (__builtin_amdgcn_ballot_w64(in_s) == 0) continue;   // (wave-uniform)
+            int cam_s, ws, hs;
+            slot_info(P, s, cam_s, ws, hs);
+            // luminance of captures (f0, f0 + 1) and (f0 + 2, f0 + 3), 16 bits each
+            uint32_t l01 = 0, l23 = 0;
+            if (in_s) {
+                int xs, ys, c0, w0, h0;
+                slot_xy<INTERP>(P, s, x, y, xs, ys, c0, w0, h0);
+                const int64_t fs = P.cam_fstride[cam_s];
+                const uint8_t *fb = P.cams[cam_s] + f0 * fs;
+#pragma unroll
+                for (int f = 0; f < kOvFrames; f++) {
+                    if (f >= nf) break;   // (uniform)
+                    const uint32_t l = luminance<CN>(fb + f * fs, ws, hs, xs, ys) << (16 * (f & 1));
+                    if (f < 2) l01 |= l;
+                    else l23 |= l;
+                }
+            }
+            for (int t = 0; t <= P.n_stages; t++) {
+                int cam_t, wt, ht;
+                slot_info(P, t, cam_t, wt, ht);
+                if (t != s && cam_t == cam_s) continue;   // (one slot per camera: nothing to pair)
+                const bool in = in_s && ((cov >> t) & 1u);
+                const uint64_t b = __builtin_amdgcn_ballot_w64(in);
+                if (b == 0) continue;                     // (wave-uniform)
+                const uint32_t s01 = wave_sum(in ? l01 : 0u, lane);
+                const uint32_t s23 = nf > 2 ? wave_sum(in ? l23 : 0u, lane) : 0u;
+                if (lane == 0) {
+                    const int seg = cam_s * MCS_MAX_CAMS + cam_t;
+                    if (count) atomicAdd(&part_n[seg], (uint32_t)__popcll(b));
+                    atomicAdd(&part_s[0][seg], s01 & 0xffffu);
+                    if (nf > 1) atomicAdd(&part_s[1][seg], s01 >> 16);
+                    if (nf > 2) atomicAdd(&part_s[2][seg], s23 & 0xffffu);
+                    if (nf > 3) atomicAdd(&part_s[3][seg], s23 >> 16);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // lane tid owns partial (i, j) = (tid / MCS_MAX_CAMS, tid % MCS_MAX_CAMS)
+    const int i = tid / MCS_MAX_CAMS, j = tid % MCS_MAX_CAMS;
+    if (i >= a.n_cams || j >= a.n_cams) return;
+    const int64_t nn = (int64_t)a.n_cams * a.n_cams, e = (int64_t)i * a.n_cams + j;
+    if (count && part_n[tid]) atomicAdd(&a.stats[e], (unsigned long long)part_n[tid]);
+#pragma unroll
+    for (int f = 0; f < kOvFrames; f++) {
+        if (f >= nf) break;
+        if (part_s[f][tid])
+            atomicAdd(&a.stats[nn + (int64_t)(f0 + f) * nn + e], (unsigned long long)part_s[f][tid]);
+    }
 }
 
 // ---- gain on source bytes (gain_half, gain_word, gain_byte: mcs_dev.h) -----------------------

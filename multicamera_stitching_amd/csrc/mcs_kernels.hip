@@ -1430,3 +1430,20 @@ MCS_DIRECT_FEATHER_ENTRIES(1)
 MCS_DIRECT_FEATHER_ENTRIES(2)
 MCS_DIRECT_FEATHER_ENTRIES(3)
 MCS_DIRECT_FEATHER_ENTRIES(4)
+
+// Table-free overlap statistics (mcs_plan_overlap_stats_direct; mcs_gain.h direct_overlap): grid
+// (dov_blocks(points), ceil(n_frames / kOvFrames)), block kDovThreads.
+#define MCS_DIRECT_OVERLAP_ENTRY(CN, IN)                                                       \
+    extern "C" __global__ __launch_bounds__(256) void mcs_direct_overlap_c##CN##_i##IN(        \
+        const mcs::KDirectOverlapArgs a)                                                       \
+    {                                                                                          \
+        mcs::direct_overlap<CN, IN>(a);                                                        \
+    }
+MCS_DIRECT_OVERLAP_ENTRY(1, 0)
+MCS_DIRECT_OVERLAP_ENTRY(1, 1)
+MCS_DIRECT_OVERLAP_ENTRY(2, 0)
+MCS_DIRECT_OVERLAP_ENTRY(2, 1)
+MCS_DIRECT_OVERLAP_ENTRY(3, 0)
+MCS_DIRECT_OVERLAP_ENTRY(3, 1)
+MCS_DIRECT_OVERLAP_ENTRY(4, 0)
+MCS_DIRECT_OVERLAP_ENTRY(4, 1)

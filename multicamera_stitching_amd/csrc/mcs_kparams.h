@@ -480,6 +480,37 @@ struct KOverlapSumArgs {
     int n_cams, n_frames;
 };
 
+// Table-free statistics (mcs_direct_overlap_c*_i*, mcs_plan_overlap_stats_direct): the same N and S
+// computed per grid point and stored nowhere.  grid (blocks, ceil(n_frames / kOvFrames)), block
+// kDovThreads: a block strides over the points, one lane per point, with 32-bit partials of N and
+// of kOvFrames captures' S in LDS (kOvSegs entries each), and adds its non-zero entries to the
+// 64-bit accumulators at the end.  The host sizes the grid for the chip (kDovBlocks), and adds
+// blocks where a block would otherwise get more than kDovMaxBlockPoints points: a point adds at
+// most 4 x 255 to an S partial and 1 to an N partial, so the partials cannot wrap.
+constexpr int kDovThreads = 256;
+constexpr int kDovBlocks = 1024;                  // grid x at most, unless the bound asks for more
+constexpr int64_t kDovMaxBlockPoints = 1ll << 22;
+static_assert(kDovMaxBlockPoints * 4 * 255 < (1ll << 32), "32-bit partials of a block");
+static_assert(kDovThreads == kOvSegs, "one lane per partial in the flush");
+// (a wave's sum of two captures' luminances travels as one dword, 16 bits each)
+static_assert(kWave * 4 * 255 < (1 << 16), "packed wave sums");
+struct KDirectOverlapArgs {
+    KParams P;                     // geometry, cams, cam_fstride (out unused)
+    unsigned long long *stats;     // N [n_cams][n_cams], then S [n_frames][n_cams][n_cams]; zeroed
+                                   // before the launch
+    int gw, gh, k;                 // grid size and step of the points (gx << k, gy << k)
+    int n_frames, n_cams;
+    int pad_;
+};
+// grid x of the launch for `points` grid points.
+constexpr unsigned dov_blocks(int64_t points)
+{
+    const int64_t fill = (points + kDovThreads - 1) / kDovThreads;
+    const int64_t bound = (points + kDovMaxBlockPoints - 1) / kDovMaxBlockPoints;
+    const int64_t want = fill < kDovBlocks ? fill : kDovBlocks;
+    return (unsigned)(want > bound ? want : bound);
+}
+
 // Gain of one camera on its source bytes (mcs_gain_apply): p' = min(255, (p q + 128) >> 8), q the
 // gain in 1/256 (256 = identity).  grid (chunks of kGainChunk bytes, frames), block kGainThreads.
 constexpr int kGainThreads = 256;

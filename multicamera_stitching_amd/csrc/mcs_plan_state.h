@@ -200,6 +200,8 @@ struct Kernels {
     // direct feather (mcs_stitch_direct on a FEATHER plan): [channels][interp], and its _g twins
     hipFunction_t direct_feather[5][2] = {};
     hipFunction_t direct_feather_g[5][2] = {};
+    // table-free overlap statistics (mcs_plan_overlap_stats_direct): [channels][interp]
+    hipFunction_t direct_overlap[5][2] = {};
 };
 
 // mcs_prepare.cpp

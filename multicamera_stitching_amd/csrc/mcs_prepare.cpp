@@ -118,6 +118,11 @@ int kernels(const Api *A, int device, const Kernels **out)
             rc = fn(name, &k.overlap_sum[c]);
         }
         if (rc == MCS_OK) rc = fn("mcs_gain_apply", &k.gain_apply);
+        for (int c = 1; c <= 4 && rc == MCS_OK; c++)
+            for (int i = 0; i < 2 && rc == MCS_OK; i++) {
+                snprintf(name, sizeof(name), "mcs_direct_overlap_c%d_i%d", c, i);
+                rc = fn(name, &k.direct_overlap[c][i]);
+            }
         if (rc) return rc;
         k.loaded = true;
     }

@@ -26,6 +26,7 @@
 // caller that keeps several jobs in flight overlaps one capture's estimation with another's.
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
@@ -148,6 +149,14 @@ struct mcs_rig_job {
     int captures_device = 0, captures_calls = 0;   // captures finished by each path
     // blend mode of the per-capture plan of wait_stitch (mcs_rig_job_set_blend)
     int blend = MCS_BLEND_NONE;
+    // per-capture exposure gains of wait_stitch (mcs_rig_job_set_exposure): the grid step (< 0:
+    // off), the solver's constants, the last call's gains and their q (n_caps x n_cams), and the
+    // statistics' buffers (n_caps x (N, S): device and pinned host; allocated on first use)
+    int exp_step = -1;
+    double exp_alpha = 0.01, exp_beta = 100.0;
+    std::vector<double> gains;
+    std::vector<uint16_t> gain_q;
+    int64_t *d_stats = nullptr, *h_stats = nullptr;
 };
 
 namespace {
@@ -391,6 +400,25 @@ void device_release(mcs_rig_job *j)
     if (d.host) (void)A->hipHostFree(d.host);
     if (d.s) (void)A->hipStreamDestroy(d.s);
     d = RigDevice();
+    if (j->d_stats) (void)A->hipFree(j->d_stats);
+    if (j->h_stats) (void)A->hipHostFree(j->h_stats);
+    j->d_stats = j->h_stats = nullptr;
+}
+
+// The statistics' buffers of a job with exposure enabled: n_caps x (N, S of one frame).
+int exposure_buffers(mcs_rig_job *j)
+{
+    if (j->d_stats && j->h_stats) return MCS_OK;
+    int rc = MCS_OK;
+    const mcs::rt::Api *A = api_for(j->device, &rc);
+    if (rc) return rc;
+    mcs::DeviceGuard dg(A, j->device);
+    if (dg.err != hipSuccess)
+        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", j->device, A->hipGetErrorString(dg.err));
+    const size_t bytes = (size_t)j->n_caps * 2 * j->n_cams * j->n_cams * sizeof(int64_t);
+    if (!j->d_stats) HIP_TRY(A->hipMalloc((void **)&j->d_stats, bytes));
+    if (!j->h_stats) HIP_TRY(A->hipHostMalloc((void **)&j->h_stats, bytes, 0));
+    return MCS_OK;
 }
 
 // The per-capture resets (candidate counts, kNN-2 keys): stream-ordered memsets issued before
@@ -619,6 +647,8 @@ int mcs_rig_job_create_batch(int n_cams, int n_captures, int w, int h, int chann
     j->n_inliers.assign(ci - 1, 0);
     j->prc.assign(ci - 1, MCS_OK);
     j->perr.assign(ci - 1, std::string());
+    j->gains.assign(ci, 1.0);
+    j->gain_q.assign(ci, 256);
     j->need.reset(new (std::nothrow) std::atomic<int>[ci - 1]);
     if (!j->need) {
         delete j;
@@ -698,8 +728,13 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
     std::vector<int> ok((size_t)np * j->n_caps);
     int rc = mcs_rig_job_wait(j, H.data(), ok.data(), n_keypoints, n_matches, n_inliers);
     if (rc) return rc;
-    for (int q = 0; q < j->n_caps; q++) {
+    for (int q = 0; q < j->n_caps; q++)
         if (!d_out[q]) return mcs::fail(MCS_E_INVALID, "mcs_rig_job_wait_stitch: NULL output %d", q);
+    int64_t fs[MCS_MAX_CAMS];
+    for (int i = 0; i < N; i++) fs[i] = (int64_t)j->w * j->h * j->channels;
+    // Capture q's plan: the pairs the job estimated into H_io / ok_io, the chain, the blend mode;
+    // the mosaic must fit the output.
+    const auto make_plan = [&](int q, mcs_plan **out) -> int {
         // a pair whose estimate failed keeps the caller's -- the previous capture's -- homography
         for (int k = 0; k < np; k++)
             if (ok[q * np + k]) {
@@ -709,31 +744,77 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         mcs_stage_desc st[MCS_MAX_CAMS];
         int cw[MCS_MAX_CAMS], ch[MCS_MAX_CAMS];
         for (int c = 0; c < N; c++) cw[c] = j->w, ch[c] = j->h;
-        rc = mcs_chain_stages(N, cw, ch, H_io, ok_io, super_mode, st);
-        if (rc) return rc;
+        int r = mcs_chain_stages(N, cw, ch, H_io, ok_io, super_mode, st);
+        if (r) return r;
         mcs_plan *plan = nullptr;
-        rc = mcs_plan_create(st, np, j->w, j->h, j->channels, interp, j->device, &plan);
-        if (rc) return rc;
+        r = mcs_plan_create(st, np, j->w, j->h, j->channels, interp, j->device, &plan);
+        if (r) return r;
         int w = 0, h = 0, c = 0;
-        if (j->blend != MCS_BLEND_NONE) rc = mcs_plan_set_blend(plan, j->blend);
-        if (rc == MCS_OK) rc = mcs_plan_out_shape(plan, &w, &h, &c);
-        if (rc == MCS_OK && ((int64_t)w * c > out_pitch || (int64_t)h * out_pitch > out_capacity))
-            rc = mcs::fail(MCS_E_SHAPE, "mosaic %d x %d does not fit the output (pitch %lld, "
-                           "%lld bytes)", w, h, (long long)out_pitch, (long long)out_capacity);
-        if (rc == MCS_OK) {
-            int64_t fs[MCS_MAX_CAMS];
-            for (int i = 0; i < N; i++) fs[i] = (int64_t)j->w * j->h * j->channels;
+        if (j->blend != MCS_BLEND_NONE) r = mcs_plan_set_blend(plan, j->blend);
+        if (r == MCS_OK) r = mcs_plan_out_shape(plan, &w, &h, &c);
+        if (r == MCS_OK && ((int64_t)w * c > out_pitch || (int64_t)h * out_pitch > out_capacity))
+            r = mcs::fail(MCS_E_SHAPE, "mosaic %d x %d does not fit the output (pitch %lld, "
+                          "%lld bytes)", w, h, (long long)out_pitch, (long long)out_capacity);
+        out_w[q] = w;
+        out_h[q] = h;
+        if (r) {
+            mcs_plan_destroy(plan);
+            return r;
+        }
+        *out = plan;
+        return MCS_OK;
+    };
+    if (j->exp_step < 0) {
+        for (int q = 0; q < j->n_caps; q++) {
+            mcs_plan *plan = nullptr;
+            rc = make_plan(q, &plan);
+            if (rc) return rc;
             // (the plan's geometry travels in the kernel arguments: it may go right after the
             // launch)
             rc = mcs_stitch_direct(plan, j->frames.data() + (size_t)q * N, fs, d_out[q], out_pitch,
-                                   out_pitch * h, 1, stream);
+                                   out_pitch * out_h[q], 1, stream);
+            mcs_plan_destroy(plan);
+            if (rc) return rc;
         }
-        mcs_plan_destroy(plan);
-        out_w[q] = w;
-        out_h[q] = h;
-        if (rc) return rc;
+        return MCS_OK;
     }
-    return MCS_OK;
+    // Exposure: carrying H_io from capture to capture is host work, so the captures' statistics
+    // are all enqueued first (sweep 1), read back with one copy and one synchronise of `stream`,
+    // and only then solved and stitched (sweep 2).
+    rc = exposure_buffers(j);
+    if (rc) return rc;
+    const size_t per = 2 * (size_t)N * N;   // N, then S of the capture's one frame
+    std::vector<mcs_plan *> plans(j->n_caps, nullptr);
+    for (int q = 0; q < j->n_caps && rc == MCS_OK; q++) {
+        rc = make_plan(q, &plans[q]);
+        if (rc == MCS_OK)
+            rc = mcs_plan_overlap_stats_direct_async(plans[q], j->frames.data() + (size_t)q * N, fs,
+                                                     1, j->exp_step, j->d_stats + q * per, stream);
+    }
+    const mcs::rt::Api *A = mcs::rt::api();
+    if (rc == MCS_OK) {
+        mcs::DeviceGuard dg(A, j->device);
+        hipError_t e = dg.err;
+        if (e == hipSuccess)
+            e = A->hipMemcpyAsync(j->h_stats, j->d_stats, j->n_caps * per * sizeof(int64_t),
+                                  hipMemcpyDeviceToHost, (hipStream_t)stream);
+        const hipError_t e2 = A->hipStreamSynchronize((hipStream_t)stream);
+        if (e != hipSuccess || e2 != hipSuccess)
+            rc = mcs::fail(MCS_E_HIP, "rig exposure statistics: %s",
+                           A->hipGetErrorString(e != hipSuccess ? e : e2));
+    }
+    for (int q = 0; q < j->n_caps && rc == MCS_OK; q++) {
+        double *g = j->gains.data() + (size_t)q * N;
+        const int64_t *st = j->h_stats + q * per;
+        rc = mcs_gain_solve_host(N, st, st + (size_t)N * N, j->channels, j->exp_alpha, j->exp_beta, g);
+        if (rc == MCS_OK) rc = mcs_plan_set_gains(plans[q], g);
+        if (rc == MCS_OK) rc = mcs_plan_gains(plans[q], j->gain_q.data() + (size_t)q * N, nullptr);
+        if (rc == MCS_OK)
+            rc = mcs_stitch_direct_gained(plans[q], j->frames.data() + (size_t)q * N, fs, d_out[q],
+                                          out_pitch, out_pitch * out_h[q], 1, stream);
+    }
+    for (mcs_plan *plan : plans) mcs_plan_destroy(plan);
+    return rc;
 }
 
 int mcs_rig_job_wait_stitch(mcs_rig_job *j, double *H_io, int *ok_io, int super_mode, int interp,
@@ -757,6 +838,35 @@ int mcs_rig_job_set_blend(mcs_rig_job *j, int mode)
         return mcs::fail(MCS_E_INVALID, "blend mode %d: a rig job stitches with the direct path "
                          "(NONE, SEAM or FEATHER)", mode);
     j->blend = mode;
+    return MCS_OK;
+}
+
+int mcs_rig_job_set_exposure(mcs_rig_job *j, int step_log2, double alpha, double beta)
+{
+    mcs::clear_error();
+    if (!j) return mcs::fail(MCS_E_INVALID, "NULL job");
+    if (step_log2 > 4) return mcs::fail(MCS_E_INVALID, "step_log2 %d (0..4, or < 0: off)", step_log2);
+    if (!std::isfinite(alpha) || !std::isfinite(beta))
+        return mcs::fail(MCS_E_INVALID, "alpha / beta");
+    j->exp_step = step_log2 < 0 ? -1 : step_log2;
+    j->exp_alpha = alpha > 0.0 ? alpha : 0.01;
+    j->exp_beta = beta > 0.0 ? beta : 100.0;
+    if (j->exp_step < 0) {
+        j->gains.assign(j->ci, 1.0);
+        j->gain_q.assign(j->ci, 256);
+    }
+    return MCS_OK;
+}
+
+int mcs_rig_job_gains(const mcs_rig_job *j, double *gains, uint16_t *q, int *enabled)
+{
+    mcs::clear_error();
+    if (!j) return mcs::fail(MCS_E_INVALID, "NULL job");
+    if (enabled) *enabled = j->exp_step >= 0 ? 1 : 0;
+    for (int i = 0; i < j->ci; i++) {
+        if (gains) gains[i] = j->gains[i];
+        if (q) q[i] = j->gain_q[i];
+    }
     return MCS_OK;
 }
 

@@ -155,8 +155,17 @@ class CaptureEstimator:
                  fast_threshold: int = 20, ratio: float = 0.75, reproj_thresh: float = 3.0,
                  iters: int = 2000, seed: int = 0, super_mode: bool = False,
                  interp: int = _capi.MCS_INTER_LINEAR, device: int = 0, threads: int = None,
-                 captures_per_job: int = 1, blend: int = _capi.MCS_BLEND_NONE):
+                 captures_per_job: int = 1, blend: int = _capi.MCS_BLEND_NONE,
+                 exposure: int = None):
         self.n_cams, self.w, self.h, self.c = n_cams, width, height, channels
+        # per-capture exposure gains of collect_stitch (mcs_rig_job_set_exposure): the grid step
+        # step_log2 (0..4) of the overlap statistics, or None for none; .gains: the last
+        # capture's gains after collect_stitch (captures_per_job > 1: the job's last capture)
+        if exposure is not None and not 0 <= int(exposure) <= 4:
+            raise ValueError(f"exposure step_log2 {exposure}: 0..4, or None")
+        self.exposure = None if exposure is None else int(exposure)
+        self.gains = np.ones(n_cams, np.float64)
+        self.gains_q = np.full(n_cams, 256, np.uint16)
         # blend mode of the capture's direct stitch (stitch / collect_stitch): NONE (the paste),
         # SEAM or FEATHER
         if blend not in (_capi.MCS_BLEND_NONE, _capi.MCS_BLEND_SEAM, _capi.MCS_BLEND_FEATHER):
@@ -196,6 +205,8 @@ class CaptureEstimator:
                                             self.device, captures=self.batch)
             if self.blend != _capi.MCS_BLEND_NONE:
                 self._jobs[slot].set_blend(self.blend)
+            if self.exposure is not None:
+                self._jobs[slot].set_exposure(self.exposure)
         return self._jobs[slot]
 
     def submit(self, frame_ptrs, wait_event: int = 0, slot: int = 0):
@@ -241,6 +252,10 @@ class CaptureEstimator:
                                            out_capacity, stream, self.super_mode, self.interp)
         for k in range(self.n_cams - 1):
             self.last_H[k] = self._Hio[k].reshape(3, 3).copy() if self._okio[k] else None
+        if self.exposure is not None:
+            g, q, _ = self._jobs[slot].gains()
+            self.gains = g.reshape(-1, self.n_cams)[-1].copy()
+            self.gains_q = q.reshape(-1, self.n_cams)[-1].copy()
         if self.batch > 1:
             self.stats = out[-1][1]
             return [shape for shape, _ in out]

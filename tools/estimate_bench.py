@@ -98,8 +98,12 @@ BLENDS = {"none": 0, "seam": 3, "feather": 1}
 BLEND_NAMES = {"none": "paste", "seam": "seam", "feather": "feather"}
 
 
-def cpu_render(oracle, plan, frames, blend):
-    """The CPU restatement of the mosaic the capture's stitch rendered."""
+def cpu_render(oracle, plan, frames, blend, q=None):
+    """The CPU restatement of the mosaic the capture's stitch rendered; q: the capture's
+    quantised exposure gains (--exposure), applied to the frames first."""
+    if q is not None:
+        frames = [np.minimum(255, (f.astype(np.int64) * int(g) + 128) >> 8).astype(np.uint8)
+                  for f, g in zip(frames, q)]
     if blend == "none":
         return oracle.flat_stitch(plan.describe(), frames)
     return oracle.blend_stitch(plan.describe(), frames, BLENDS[blend])
@@ -140,14 +144,31 @@ def main():
     ap.add_argument("--blend", choices=("none", "seam", "feather"), default="none",
                     help="with --stitch: blend mode of the capture's direct stitch (none: the "
                          "paste; seam; feather: mcs_direct_feather_*)")
+    ap.add_argument("--exposure", type=int, default=None, metavar="K",
+                    help="with --stitch --pipelined --overlap (the in-library stitch): per-capture "
+                         "exposure gains from the table-free overlap statistics on the 2^K grid "
+                         "(mcs_rig_job_set_exposure), fused into the capture's stitch")
+    ap.add_argument("--camera-scales", default=None, metavar="S0,S1,..",
+                    help="scale camera i's frame bytes by Si (clipped to 255): cameras on different "
+                         "exposures, so that --exposure finds gains other than 1")
     ap.add_argument("--pinned", action="store_true",
                     help="camera frames in pinned host buffers (default: pageable numpy arrays, "
                          "as the reference's capture loop holds them)")
     args = ap.parse_args()
+    if args.exposure is not None and not (args.stitch and args.pipelined and args.overlap and
+                                          not args.python_stitch):
+        raise SystemExit("--exposure needs --stitch --pipelined --overlap and the in-library "
+                         "stitch")
     from multicamera_stitching_amd import rig
     W, Hh, N = 1920, 1080, 4
     C = rig.camera_models(N, W, Hh, seed=0)
     frames = rig.world_frames(C, W, Hh, 3, seed=0, world_fn=world)
+    if args.camera_scales:
+        scales = [float(v) for v in args.camera_scales.split(",")]
+        if len(scales) != N:
+            raise SystemExit("--camera-scales needs %d values" % N)
+        frames = [np.clip(np.rint(f.astype(np.float64) * v), 0, 255).astype(np.uint8)
+                  for f, v in zip(frames, scales)]
     if args.pinned:
         import torch
         pinned = []
@@ -314,7 +335,8 @@ def pipelined_main(args, frames, truth, W, Hh, N):
     for e in ev_done:
         e.record(sts[0])
     est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
-                                    captures_per_job=B, blend=BLENDS[args.blend])
+                                    captures_per_job=B, blend=BLENDS[args.blend],
+                                    exposure=args.exposure)
     pending = [None] * D          # plan of the capture last stitched from frame set / output i
     lat = []
 
@@ -409,7 +431,8 @@ def pipelined_main(args, frames, truth, W, Hh, N):
             link = reps * sum(h.numel() for h in host) / (time.perf_counter() - tl) / 1e9
     ow, oh = plan.out_w, plan.out_h
     got = out[slot][:oh, :ow * 3].cpu().numpy().reshape(oh, ow, 3)
-    want = cpu_render(oracle, plan, frames, args.blend)
+    want = cpu_render(oracle, plan, frames, args.blend,
+                      est.gains_q if args.exposure is not None else None)
     for q in pending:
         if q is not None:
             q.close()
@@ -433,6 +456,9 @@ def pipelined_main(args, frames, truth, W, Hh, N):
                                   "previous captures are estimated and stitched",
                    "pipeline_depth": D, "rig_jobs": bool(args.overlap),
                    "captures_per_rig_job": B, "stitch_streams": len(sts),
+                   "exposure_step_log2": args.exposure, "camera_scales": args.camera_scales,
+                   "exposure_gains_last_capture": [round(float(g), 6) for g in est.gains]
+                   if args.exposure is not None else None,
                    "host_threads": args.threads},
         "frames_resident_in_hbm": bool(args.resident),
         "h2d_gb_per_s": None if link is None else
