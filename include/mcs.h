@@ -426,8 +426,10 @@ int mcs_match_hamming_knn2_host(const uint8_t *query, int n_query, const uint8_t
  * ORB keypoints + 256-bit descriptors of one image (u8, channels 1 = gray or 3 = BGR, dense),
  * the per-frame replacement of detectAndDescribe (StitcherClass.py:356-403, SIFT there):
  * nlevels pyramid (scale_factor, INTER_LINEAR), FAST-9 (fast_threshold) + NMS, Harris ranking
- * with OpenCV's per-level quota of nfeatures, intensity-centroid orientation, rBRIEF (OpenCV's
- * 31x31 pattern).  Specified in csrc/mcs_orb_core.h.  Outputs (capacity nfeatures): kp_xy
+ * with OpenCV's per-level quota of nfeatures (each level's share capped by what is left, so the
+ * quotas never add up to more than nfeatures), intensity-centroid orientation, rBRIEF (OpenCV's
+ * 31x31 pattern).  Specified in csrc/mcs_orb_core.h.  Outputs (capacity nfeatures entries each;
+ * *n_out <= nfeatures, nothing is written past entry *n_out): kp_xy
  * (level-0 pixels), kp_response, kp_angle (degrees), kp_level (may be NULL), desc (32 B each),
  * *n_out.  w, h <= 65535.  Synchronous: one upload, one copy back (levels ranked on the device;
  * a level with more than 4096 candidates is ranked on the host, same result). */

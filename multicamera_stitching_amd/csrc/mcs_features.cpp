@@ -544,12 +544,14 @@ int mcs::feat::orb_geom(int w, int h, int nfeatures, int nlevels, float scale_fa
     const float factor = (float)(1.0 / scale_factor);
     float per = nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)nlevels));
     int sum = 0;
+    // (each level's rounded share capped by what is left: the roundings can add up to more than
+    // nfeatures -- 15 for 14 features on 11 levels --, and the callers' arrays hold nfeatures)
     for (int l = 0; l < nlevels - 1; l++) {
-        g->quota[l] = (int)std::lrint(per);
+        g->quota[l] = std::min((int)std::lrint(per), nfeatures - sum);
         sum += g->quota[l];
         per *= factor;
     }
-    g->quota[nlevels - 1] = std::max(nfeatures - sum, 0);
+    g->quota[nlevels - 1] = nfeatures - sum;
     g->n_bound = 0;
     g->cap_total = 0;
     for (int l = 0; l < nlevels; l++) {

@@ -12,7 +12,12 @@
 //   Harris       a, b, c = sums over the 7x7 block of Ix^2, Iy^2, IxIy (3x3 Sobel, integers),
 //                response = (double)(a b - c^2) - 0.04 ((double)(a + b))^2;
 //   ranking      per level by response (desc), then y, then x; the per-level quota is
-//                OpenCV's geometric split of nfeatures (float arithmetic as OpenCV);
+//                OpenCV's geometric split of nfeatures (float arithmetic as OpenCV), each level's
+//                rounded share capped by what the levels before it left:
+//                quota[l] = min(lrint(per_l), nfeatures - sum quota[< l]) for l < nlevels - 1, the
+//                last level the remainder -- so sum quota <= nfeatures always (OpenCV's uncapped
+//                roundings add up to as much as nfeatures + 3 for small nfeatures), and OpenCV's
+//                quotas wherever those stay within nfeatures;
 //   orientation  m10, m01 over OpenCV's umax disk (integers); r = sqrt(m10^2 + m01^2),
 //                (cos, sin) = (m10 / r, m01 / r) ((1, 0) when r = 0);
 //   blur         7-tap integer kernel [18 34 49 54 49 34 18] / 256 (sigma ~2), horizontal then

@@ -69,7 +69,14 @@ static double harris(const uint8_t *p, int st)
     return (double)(a * b - c * c) - 0.04 * (t * t);
 }
 
-static int refl(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+/* reflect-101; on a level narrower than the blur's 4 taps the position is first held to the one
+ * reflection the image has (levels that small carry no keypoint, so no value of theirs is used) */
+static int refl(int i, int n)
+{
+    if (i < -(n - 1)) i = -(n - 1);
+    if (i > 2 * n - 2) i = 2 * n - 2;
+    return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i);
+}
 
 /* Returns the number of keypoints written (<= nfeatures).  kp_level/xy/response/cs_sn may be
  * used for parity: cs_sn holds the orientation's (cos, sin). */
@@ -93,13 +100,15 @@ int orc_orb_detect(const uint8_t *gray, int w, int h, int nfeatures, int nlevels
     {
         float factor = (float)(1.0 / scale_factor);
         float per = nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)nlevels));
-        int sum = 0;
+        /* a level takes its rounded share, or what the levels before it left of nfeatures */
+        int left = nfeatures;
         for (int l = 0; l < nlevels - 1; l++) {
-            quota[l] = (int)lrintf(per);
-            sum += quota[l];
+            const int share = (int)lrintf(per);
+            quota[l] = share < left ? share : left;
+            left -= quota[l];
             per *= factor;
         }
-        quota[nlevels - 1] = nfeatures - sum > 0 ? nfeatures - sum : 0;
+        quota[nlevels - 1] = left;
     }
     int n = 0;
     const int E = 31;

@@ -1,0 +1,126 @@
+"""The feature edge-case table (tests/feature_edges.py) on the CPU oracle alone: every case shows
+the property it is in the table for -- so that the GPU comparison on the same table cannot pass on
+an empty result --, no level of any ORB case holds as many candidates as the product's candidate
+buffer (above that the product drops candidates in atomic order and has no defined answer), and
+the matcher / RANSAC cases have the answers the table states."""
+import numpy as np
+import pytest
+
+import feature_edges as fe
+from oracle import oracle
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in fe.ORB_CASES])
+def test_orb_case_shows_its_property(name):
+    case = fe.ORB_BY_NAME[name]
+    img = case["image"]()
+    h, w = img.shape
+    assert h <= 800 and w <= 800 and h * w <= 600 * 800
+    res = oracle.orb_detect(img, threshold=case["threshold"], **fe.orb_kwargs(case))
+    fe.check_orb_property(case, res)
+    # the oracle keeps within nfeatures on its own arrays (it did not for 14 features on 11
+    # levels: its uncapped quotas summed to 15)
+    assert len(res["xy"]) <= case["nfeatures"]
+    cand = fe.case_candidates(case)
+    caps = fe.candidate_caps(w, h, case["nlevels"], case["scale_factor"])
+    print(name, "candidates", cand, "caps", caps)
+    assert all(c < cap for c, cap in zip(cand, caps)), (cand, caps)
+
+
+def test_ranking_boundary_cases_sit_on_the_boundary():
+    """4096 candidates rank on the device, 4097 on the host; 64|65 and 128|129 step the sort
+    network's padded size."""
+    for K in fe.LATTICE_K:
+        assert fe.case_candidates(fe.ORB_BY_NAME[f"lattice_{K}"]) == [K]
+    assert fe.SEL_MAX in fe.LATTICE_K and fe.SEL_MAX + 1 in fe.LATTICE_K
+
+
+def test_scale_cases_take_both_pyramid_paths():
+    """The table holds scale cases for the one-launch pyramid and for the per-level resize chain
+    (check_orb_property holds each to its path)."""
+    chain = [c["chain"] for c in fe.ORB_CASES if "chain" in c]
+    assert chain.count(False) >= 3 and chain.count(True) >= 3
+
+
+def test_hamming_cases():
+    q, t, idx, dist = fe.hamming_complement()
+    gi, gd = oracle.hamming_knn2(q, t)
+    assert np.array_equal(gi, idx) and np.array_equal(gd, dist)
+    for nq in (1, 65):
+        q, t, idx, dist = fe.hamming_far_indices(nq)
+        assert idx.min() > 65535 and len(t) == 70000
+        gi, gd = oracle.hamming_knn2(q, t)
+        assert np.array_equal(gi, idx) and np.array_equal(gd, dist)
+    q, t, idx, dist = fe.hamming_straddle()
+    gi, gd = oracle.hamming_knn2(q, t)
+    assert np.array_equal(gi, idx) and np.array_equal(gd, dist)
+
+
+@pytest.mark.parametrize("dim", [1, 64, 128, 256])
+def test_l2_extremes(dim):
+    q, t, idx, far = fe.l2_extremes(dim)
+    gi, gd, exact = oracle.l2_knn2(q, t)
+    assert exact and np.array_equal(gi, idx)
+    assert (gd[:, 0] == 0).all() and (gd[:, 1] == far).all()
+
+
+@pytest.mark.parametrize("name", fe.RANSAC_DEGENERATE)
+def test_ransac_degenerate_cases(name):
+    src, dst, iters, seed, has_model = fe.ransac_case(name)
+    H, mask, best, scores = oracle.ransac_homography(src, dst, 3.0, iters=iters, seed=seed)
+    assert (H is not None) == has_model
+    if has_model:
+        assert best >= 0 and mask.all()
+    else:
+        assert best == -1 and (scores == -1).all() and not mask.any()
+
+
+def test_lattice_rig_pairs():
+    """The 5-camera lattice job: 0, 1, 2, 5 and 40 keypoints; no pair has a match (no train
+    keypoint; no second neighbour; then dots whose equal descriptors tie, which the strict ratio
+    test drops)."""
+    kps, pairs = fe.oracle_pairs(fe.lattice_rig(), nfeatures=64, nlevels=1)
+    assert kps == [0, 1, 2, 5, 40]
+    assert [len(s) for s, _ in pairs] == [0, 0, 0, 0]
+
+
+@pytest.mark.parametrize("w,h,seed,nfeatures", fe.RIG_SMALL)
+def test_small_rig_pairs(w, h, seed, nfeatures):
+    """What the small rigs' pairs come to on the oracle (the table's comment), and for the tied
+    cases: the best score is shared by further hypotheses in the wave of the first."""
+    from multicamera_stitching_amd import rig
+    _, frames, _ = rig.estimation_rig(3, w, h, 3, seed=seed)
+    kps, pairs = fe.oracle_pairs(frames, nfeatures, 3)
+    assert max(kps) <= nfeatures
+    got = []
+    for src, dst in pairs:
+        if len(src) <= 4:
+            got.append((len(src), None))
+            continue
+        H, mask, best, scores = oracle.ransac_homography(src, dst, 3.0, iters=2000, seed=0)
+        tied = np.nonzero(scores == scores.max())[0]
+        wave = (tied % 1024) // 64          # mcs_rig_best: 1024 threads stride the hypotheses
+        got.append((len(src), (int(scores.max()), len(tied), int((wave == wave[0]).sum()))))
+    want = {(160, 120, 2, 7): [(0, None), (0, None)],
+            (160, 120, 2, 60): [(11, (10, 25, 3)), (5, (-1, 2000, 128))],
+            (320, 240, 2, 7): [(2, None), (0, None)],
+            (320, 240, 2, 60): [(6, (-1, 2000, 128)), (4, None)]}
+    key = (w, h, seed, nfeatures)
+    if key in want:
+        assert got == want[key], got
+    else:
+        n, (score, tied, in_wave) = got[0]
+        assert n == 9 and score == 4 and tied > 100 and in_wave >= 6, got
+
+
+def test_hamming_train_limit_is_an_argument_check():
+    """2^23 train descriptors do not fit the key's 23 index bits: refused before anything touches
+    the device (the same check the native program makes on mcs_match_hamming_knn2_host)."""
+    from multicamera_stitching_amd import _capi
+    L = _capi.load()
+    d = np.zeros((1, 32), np.uint8)
+    out = np.zeros((1, 2), np.int32)
+    rc = L.mcs_match_hamming_knn2_host(d.ctypes.data, 1, d.ctypes.data, 1 << 23, out.ctypes.data,
+                                       out.ctypes.data, 0)
+    assert rc == _capi.MCS_E_INVALID
+    assert b"n_train=8388608" in L.mcs_last_error()
