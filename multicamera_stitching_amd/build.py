@@ -36,7 +36,7 @@ HOST_SRC = ["mcs_plan.cpp", "hip_rt.cpp", "mcs_runtime.cpp", "mcs_capi.cpp", "mc
 HEADERS = ["mcs_kparams.h", "mcs_dev.h", "mcs_fparams.h", "mcs_common.h", "hip_rt.h", "mcs_blend.h",
            "mcs_gain.h", "mcs_ransac_core.h",
            "mcs_orb_core.h", "mcs_orb_pattern.h", "mcs_feat_int.h", "mcs_lens_core.h",
-           "mcs_plan_state.h"]
+           "mcs_plan_state.h", "mcs_scratch.h"]
 INC = ["-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
 
 DEVICE_FLAGS = [

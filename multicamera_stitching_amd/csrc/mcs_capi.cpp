@@ -12,13 +12,13 @@
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#include "mcs_scratch.h"
 
 int mcs::plan_device(const mcs_plan *plan) { return plan ? plan->device : 0; }
 
 #define MCS_VERSION_STRING "mcs 0.1.0 (gfx950 code object, HIP module launch)"
 
 using namespace mcs::host;
-using mcs::DeviceGuard;
 using mcs::kMaxDevices;
 
 namespace mcs {
@@ -280,9 +280,8 @@ int mcs_plan_destroy(mcs_plan *p)
                    p->d_lens || p->d_cyl || p->d_map || p->d_seam || p->ov.d_table || p->ov.d_S;
     for (int i = 0; i < MCS_MAX_CAMS; i++) touched = touched || p->d_cams[i];
     if (touched) {
-        const Api *A = mcs::rt::api();
+        const mcs::Entry A(p->device);
         if (A) {
-            DeviceGuard g(A, p->device);
             if (p->stream) (void)A->hipStreamSynchronize(p->stream);
             for (int i = 0; i < MCS_MAX_CAMS; i++)
                 if (p->d_cams[i]) (void)A->hipFree(p->d_cams[i]);
@@ -336,12 +335,9 @@ int mcs_stitch_host_sized(mcs_plan *p, const uint8_t *const *cams, const int *ca
 {
     mcs::clear_error();
     if (!p || !cams || !out) return mcs::fail(MCS_E_INVALID, "NULL plan/cams/out");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     const int C = p->fd.channels;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
     int rc = ensure_stream(A, p);
     if (rc) return rc;
     rc = ensure_host_buffers(A, p);
@@ -422,11 +418,8 @@ int mcs_resize_linear_device(const uint8_t *d_src, int src_w, int src_h, int64_t
     if (src_pitch < (int64_t)src_w * channels || dst_pitch < (int64_t)dst_w * channels)
         return mcs::fail(MCS_E_INVALID, "pitch smaller than a row");
     if (n_frames == 0) return MCS_OK;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const Kernels *k = nullptr;
     int rc = kernels(A, device, &k);
     if (rc) return rc;
@@ -492,11 +485,8 @@ static int stitch_device_launch(mcs_plan *p, const uint8_t *const *d_cams,
     int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
                             n_frames, &kp);
     if (rc) return rc;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     // (identity gains, or none: exactly the ungained launch)
     return launch_stitch(A, p, kp, n_frames, (hipStream_t)stream, gained && gains_active(p));
 }
@@ -526,11 +516,8 @@ static int stitch_direct_launch(mcs_plan *p, const uint8_t *const *d_cams,
     gained = gained && gains_active(p);
     if (gained) fill_gain_q(p, &kp);
     if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames == 0) return MCS_OK;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     const Kernels *k = nullptr;
     rc = kernels(A, p->device, &k);
     if (rc) return rc;
@@ -605,12 +592,9 @@ int mcs_stitch_direct_gained(mcs_plan *p, const uint8_t *const *d_cams,
 int mcs_plan_prepare(mcs_plan *p, void *stream)
 {
     if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
     hipStream_t s = (hipStream_t)stream;
     if (!s) {
         int rc = ensure_stream(A, p);
@@ -635,9 +619,8 @@ int mcs_plan_set_blend(mcs_plan *p, int mode)
                          "NONE is not defined for it (use SEAM, FEATHER or MULTIBAND)");
     if (mode == p->blend) return MCS_OK;
     if (p->t.prepared) {
-        const Api *A = mcs::rt::api();
-        if (!A) return MCS_E_HIP;
-        DeviceGuard g(A, p->device);
+        const mcs::Entry A(p->device);
+        if (A.status) return A.status;
         release_tables(A, p);
     }
     p->blend = mode;
@@ -661,17 +644,12 @@ int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist,
     } else if (!((p->kp.lens_mask >> cam) & 1u)) {
         return MCS_OK;   // none to remove
     }
-    if (p->t.prepared) {
-        const Api *A = mcs::rt::api();
-        if (!A) return MCS_E_HIP;
-        DeviceGuard g(A, p->device);
-        release_tables(A, p);
-    }
-    if (p->ov.d_table || p->ov.d_S) {   // the overlap table holds positions through the lenses
-        const Api *A = mcs::rt::api();
-        if (!A) return MCS_E_HIP;
-        DeviceGuard g(A, p->device);
-        drop_overlap(A, p);
+    // (the overlap table holds positions through the lenses)
+    if (p->t.prepared || p->ov.d_table || p->ov.d_S) {
+        const mcs::Entry A(p->device);
+        if (A.status) return A.status;
+        if (p->t.prepared) release_tables(A, p);
+        if (p->ov.d_table || p->ov.d_S) drop_overlap(A, p);
     }
     if (K) {
         p->lens[cam] = L;
@@ -712,11 +690,8 @@ int mcs_plan_find_seams(mcs_plan *p, const uint8_t *const *cams, int method, int
         return mcs::fail(MCS_E_INVALID, "seam method %d", method);
     if (method == MCS_SEAM_GRAPHCUT && (!cams || scale_log2 < 0 || scale_log2 > 4))
         return mcs::fail(MCS_E_INVALID, "graph-cut seams need cams and scale_log2 in 0..4");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     release_tables(A, p);
     if (p->d_seam) (void)A->hipFree(p->d_seam);
     p->d_seam = nullptr;
@@ -752,51 +727,43 @@ int mcs_plan_find_seams(mcs_plan *p, const uint8_t *const *cams, int method, int
     a.k = kk;
     std::vector<uint8_t> lab(np), smp;   // (smp: host Dinic only)
     std::vector<uint16_t> cov(np);
-    hipError_t e = A->hipMalloc((void **)&a.label, np);
-    if (e == hipSuccess) e = A->hipMalloc((void **)&a.cov, np * sizeof(uint16_t));
-    if (e == hipSuccess) e = A->hipMalloc((void **)&a.samples, np * C * n);
-    if (e == hipSuccess) e = A->hipMemsetAsync(a.samples, 0, np * C * n, p->stream);
-    if (e == hipSuccess) {
-        rc = launch_args(A, k->seam_sample[C][p->fd.interp], (unsigned)((np + 255) / 256), 1,
-                         256, 1, &a, sizeof(a), p->stream);
-        if (rc) e = hipErrorLaunchFailure;
-    }
+    static const char what[] = "seam finding";
+    mcs::Scratch sc(A, p->stream);
+    HIP_TRY_AS(what, sc.dev(&a.label, np));
+    HIP_TRY_AS(what, sc.dev(&a.cov, np));
+    HIP_TRY_AS(what, sc.dev(&a.samples, np * C * n));
+    HIP_TRY_AS(what, A->hipMemsetAsync(a.samples, 0, np * C * n, p->stream));
+    rc = launch_args(A, k->seam_sample[C][p->fd.interp], (unsigned)((np + 255) / 256), 1, 256, 1,
+                     &a, sizeof(a), p->stream);
+    if (rc) return rc;
     // the pairwise cuts: push-relabel on the device (default), or the host Dinic
     // (MCS_SEAM_FLOW=host; the checker of the device path)
     static const bool host_flow =
         getenv("MCS_SEAM_FLOW") && !strcmp(getenv("MCS_SEAM_FLOW"), "host");
-    if (e == hipSuccess)
-        e = A->hipMemcpyAsync(cov.data(), a.cov, np * 2, hipMemcpyDeviceToHost, p->stream);
+    HIP_TRY_AS(what, A->hipMemcpyAsync(cov.data(), a.cov, np * 2, hipMemcpyDeviceToHost,
+                                       p->stream));
     if (host_flow) {
-        if (e == hipSuccess)
-            e = A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost, p->stream);
+        HIP_TRY_AS(what, A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost,
+                                           p->stream));
         smp.resize(np * C * n);
-        if (e == hipSuccess)
-            e = A->hipMemcpyAsync(smp.data(), a.samples, np * C * n, hipMemcpyDeviceToHost,
-                                  p->stream);
+        HIP_TRY_AS(what, A->hipMemcpyAsync(smp.data(), a.samples, np * C * n,
+                                           hipMemcpyDeviceToHost, p->stream));
     }
-    if (e == hipSuccess) e = A->hipStreamSynchronize(p->stream);
-    if (e == hipSuccess && rc == MCS_OK) {
-        if (host_flow) {
-            rc = mcs::seam_graphcut(n, gw, gh, lab.data(), cov.data(), smp.data(), C);
-            if (rc == MCS_OK)
-                e = A->hipMemcpyAsync(a.label, lab.data(), np, hipMemcpyHostToDevice, p->stream);
-        } else {
-            rc = mcs::seam_graphcut_device(p->device, p->stream, n, gw, gh, a.label, a.cov,
-                                           a.samples, C, cov.data(), p->seam_stats);
-            if (rc == MCS_OK)
-                e = A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost, p->stream);
-        }
-        if (e == hipSuccess) e = A->hipStreamSynchronize(p->stream);
-    }
-    for (void *q : {(void *)a.cov, (void *)a.samples})
-        if (q) (void)A->hipFree(q);
-    if (rc || e != hipSuccess) {
-        if (a.label) (void)A->hipFree(a.label);
+    HIP_TRY_AS(what, sc.sync());
+    if (host_flow) {
+        rc = mcs::seam_graphcut(n, gw, gh, lab.data(), cov.data(), smp.data(), C);
         if (rc) return rc;
-        return mcs::fail(MCS_E_HIP, "seam finding: %s", A->hipGetErrorString(e));
+        HIP_TRY_AS(what, A->hipMemcpyAsync(a.label, lab.data(), np, hipMemcpyHostToDevice,
+                                           p->stream));
+    } else {
+        rc = mcs::seam_graphcut_device(p->device, p->stream, n, gw, gh, a.label, a.cov, a.samples,
+                                       C, cov.data(), p->seam_stats);
+        if (rc) return rc;
+        HIP_TRY_AS(what, A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost,
+                                           p->stream));
     }
-    p->d_seam = a.label;   // the device labels (the seam grid the stitch kernels read)
+    HIP_TRY_AS(what, sc.sync());
+    p->d_seam = sc.keep(a.label);   // the device labels (the seam grid the stitch kernels read)
     p->seam_lab.swap(lab);
     p->seam_w = gw;
     p->seam_h = gh;
@@ -819,6 +786,31 @@ int mcs_seam_graphcut_host(int n_cams, int gw, int gh, uint8_t *labels, const ui
     return mcs::seam_graphcut(n_cams, gw, gh, labels, cover, samples, channels);
 }
 
+// mcs_seam_graphcut_device on its stream s, after the checks.
+static int graphcut_on_stream(const Api *A, hipStream_t s, int n_cams, int gw, int gh,
+                              uint8_t *labels, const uint16_t *cover, const uint8_t *samples,
+                              int channels, int device, int64_t *stats)
+{
+    static const char what[] = "seam graph cut";
+    const size_t np = (size_t)gw * gh, sb = np * n_cams * channels;
+    mcs::Scratch sc(A, s);
+    uint8_t *buf = nullptr;
+    HIP_TRY_AS(what, sc.dev(&buf, np * 3 + sb + 16));
+    uint8_t *d_lab = buf, *d_smp = buf + np * 3 + 16;
+    uint16_t *d_cov = reinterpret_cast<uint16_t *>(buf + ((np + 7) & ~(size_t)7));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_lab, labels, np, hipMemcpyHostToDevice, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_cov, cover, np * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_smp, samples, sb, hipMemcpyHostToDevice, s));
+    const int rc = mcs::seam_graphcut_device(device, s, n_cams, gw, gh, d_lab, d_cov, d_smp,
+                                             channels, cover, stats);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(labels, d_lab, np, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, sc.sync());
+    // (this entry point has always synchronised twice here: the runtime sees the calls it saw)
+    HIP_TRY_AS(what, sc.sync());
+    return MCS_OK;
+}
+
 int mcs_seam_graphcut_device(int n_cams, int gw, int gh, uint8_t *labels, const uint16_t *cover,
                              const uint8_t *samples, int channels, int device, int64_t *stats)
 {
@@ -828,34 +820,14 @@ int mcs_seam_graphcut_device(int n_cams, int gw, int gh, uint8_t *labels, const 
         (int64_t)gw * gh > (int64_t)1 << 28)
         return mcs::fail(MCS_E_INVALID, "n_cams %d, grid %dx%d, channels %d", n_cams, gw, gh,
                          channels);
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
-    const size_t np = (size_t)gw * gh, sb = np * n_cams * channels;
-    uint8_t *buf = nullptr;
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     hipStream_t s = nullptr;
     HIP_TRY(A->hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    hipError_t e = A->hipMalloc((void **)&buf, np * 3 + sb + 16);
-    uint8_t *d_lab = buf, *d_smp = buf + np * 3 + 16;
-    uint16_t *d_cov = reinterpret_cast<uint16_t *>(buf + ((np + 7) & ~(size_t)7));
-    if (e == hipSuccess) e = A->hipMemcpyAsync(d_lab, labels, np, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = A->hipMemcpyAsync(d_cov, cover, np * 2, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = A->hipMemcpyAsync(d_smp, samples, sb, hipMemcpyHostToDevice, s);
-    int rc = MCS_OK;
-    if (e == hipSuccess)
-        rc = mcs::seam_graphcut_device(device, s, n_cams, gw, gh, d_lab, d_cov, d_smp, channels,
-                                       cover, stats);
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(labels, d_lab, np, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = A->hipStreamSynchronize(s);
-    (void)A->hipStreamSynchronize(s);
-    if (buf) (void)A->hipFree(buf);
+    const int rc = graphcut_on_stream(A, s, n_cams, gw, gh, labels, cover, samples, channels,
+                                      device, stats);
     (void)A->hipStreamDestroy(s);
-    if (rc) return rc;
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "seam graph cut: %s", A->hipGetErrorString(e));
-    return MCS_OK;
+    return rc;
 }
 
 int mcs_plan_seam_stats(const mcs_plan *p, int64_t *stats)
@@ -896,11 +868,8 @@ int mcs_plan_footprint(mcs_plan *p, int64_t *touched_px, int n_cams)
     if (!p || !touched_px) return mcs::fail(MCS_E_INVALID, "NULL plan/touched_px");
     if (n_cams < p->fd.n_cams)
         return mcs::fail(MCS_E_INVALID, "n_cams %d < %d", n_cams, p->fd.n_cams);
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     int rc = ensure_stream(A, p);
     if (rc) return rc;
     const Kernels *k = nullptr;
@@ -909,39 +878,35 @@ int mcs_plan_footprint(mcs_plan *p, int64_t *touched_px, int n_cams)
     rc = upload_plan_tables(A, p, p->stream);
     if (rc) return rc;
     const int n = p->fd.n_cams;
+    static const char what[] = "footprint";
     uint8_t *masks[MCS_MAX_CAMS] = {};
     uint8_t **d_masks = nullptr;
     unsigned long long *d_counts = nullptr;
     unsigned long long counts[MCS_MAX_CAMS] = {};
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < n && e == hipSuccess; i++) {
-        const size_t bytes = ((size_t)p->fd.cam_w[i] * p->fd.cam_h[i] + 3) / 4 * 4;
-        e = A->hipMalloc((void **)&masks[i], bytes > 0 ? bytes : 4);
-        if (e == hipSuccess) e = A->hipMemsetAsync(masks[i], 0, bytes > 0 ? bytes : 4, p->stream);
+    mcs::Scratch sc(A, p->stream);
+    for (int i = 0; i < n; i++) {
+        const size_t px = (size_t)p->fd.cam_w[i] * p->fd.cam_h[i];
+        const size_t bytes = px > 0 ? (px + 3) / 4 * 4 : 4;
+        HIP_TRY_AS(what, sc.dev(&masks[i], bytes));
+        HIP_TRY_AS(what, A->hipMemsetAsync(masks[i], 0, bytes, p->stream));
     }
-    if (e == hipSuccess) e = A->hipMalloc((void **)&d_masks, sizeof(masks));
-    if (e == hipSuccess) e = A->hipMalloc((void **)&d_counts, sizeof(counts));
-    if (e == hipSuccess)
-        e = A->hipMemcpyAsync(d_masks, masks, sizeof(masks), hipMemcpyHostToDevice, p->stream);
-    if (e == hipSuccess) e = A->hipMemsetAsync(d_counts, 0, sizeof(counts), p->stream);
-    if (e == hipSuccess && p->fd.out_w > 0 && p->fd.out_h > 0) {
+    HIP_TRY_AS(what, sc.dev(&d_masks, MCS_MAX_CAMS));
+    HIP_TRY_AS(what, sc.dev(&d_counts, MCS_MAX_CAMS));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_masks, masks, sizeof(masks), hipMemcpyHostToDevice,
+                                       p->stream));
+    HIP_TRY_AS(what, A->hipMemsetAsync(d_counts, 0, sizeof(counts), p->stream));
+    if (p->fd.out_w > 0 && p->fd.out_h > 0) {
         mcs::KFootprintArgs args;
         args.P = p->kp;
         args.masks = d_masks;
         args.counts = d_counts;
         rc = launch_args(A, k->footprint[p->fd.interp], (p->fd.out_w + 255) / 256, p->fd.out_h,
                          256, 1, &args, sizeof(args), p->stream);
+        if (rc) return rc;
     }
-    if (rc) e = hipErrorLaunchFailure;   // (skip to the clean-up; rc is what is returned)
-    if (e == hipSuccess)
-        e = A->hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = A->hipStreamSynchronize(p->stream);
-    for (int i = 0; i < n; i++)
-        if (masks[i]) (void)A->hipFree(masks[i]);
-    if (d_masks) (void)A->hipFree(d_masks);
-    if (d_counts) (void)A->hipFree(d_counts);
-    if (rc) return rc;
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "footprint: %s", A->hipGetErrorString(e));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost,
+                                       p->stream));
+    HIP_TRY_AS(what, sc.sync());
     for (int i = 0; i < n_cams; i++) touched_px[i] = i < n ? (int64_t)counts[i] : 0;
     return MCS_OK;
 }
@@ -959,15 +924,12 @@ extern "C" int mcs__plan_tile_tables(const mcs_plan *p, void *tiles_out, uint16_
     mcs::clear_error();
     if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
     if (!p->t.prepared) return mcs::fail(MCS_E_INVALID, "the plan is not prepared");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     const size_t tiles = (size_t)p->gx * p->gy;
     if (!tiles_out || !spans_out || !desc_out || (size_t)std::max(max_tiles, 0) < tiles ||
         tiles == 0)
         return (int)tiles;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
     // (prepare synchronised after building them; the copies run on the null stream)
     HIP_TRY(A->hipMemcpyAsync(tiles_out, p->t.d_tiles, tiles * sizeof(mcs::TileHdr),
                               hipMemcpyDeviceToHost, nullptr));

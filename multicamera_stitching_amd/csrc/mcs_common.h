@@ -9,13 +9,15 @@
 #include "mcs_kparams.h"
 #include "mcs_lens_core.h"
 
-// Returns MCS_E_HIP with the HIP error text when `expr` fails (needs `A`, the bound runtime).
-#define HIP_TRY(expr)                                                                          \
+// Returns MCS_E_HIP with "<what>: <HIP error text>" when `expr` fails (needs `A`, the bound
+// runtime); HIP_TRY: what = the expression itself, "... failed".
+#define HIP_TRY_AS(what, expr)                                                                 \
     do {                                                                                       \
         hipError_t e_ = (expr);                                                                \
         if (e_ != hipSuccess)                                                                  \
-            return mcs::fail(MCS_E_HIP, "%s failed: %s", #expr, A->hipGetErrorString(e_));   \
+            return mcs::fail(MCS_E_HIP, "%s: %s", what, A->hipGetErrorString(e_));           \
     } while (0)
+#define HIP_TRY(expr) HIP_TRY_AS(#expr " failed", expr)
 
 namespace mcs {
 
@@ -76,6 +78,7 @@ struct DeviceGuard {
     hipError_t err = hipSuccess;
     DeviceGuard(const rt::Api *a, int dev) : A(a)
     {
+        if (!A) return;   // (no runtime bound: nothing to set, nothing to restore)
         err = A->hipGetDevice(&prev);
         if (err == hipSuccess && prev != dev) err = A->hipSetDevice(dev);
     }
@@ -83,6 +86,28 @@ struct DeviceGuard {
     {
         if (prev >= 0) (void)A->hipSetDevice(prev);
     }
+};
+
+// The prologue of an entry point that uses the device: binds the runtime and makes `dev` current
+// until the call returns.  Named `A` it stands for the bound runtime in what follows (A->hipX(...),
+// HIP_TRY, an `const rt::Api *` argument):
+//     const mcs::Entry A(dev);
+//     if (A.status) return A.status;
+// status: MCS_OK, or what the entry point returns (mcs_last_error() set).
+struct Entry {
+    const rt::Api *const api = rt::api();
+    const DeviceGuard guard;
+    int status = MCS_OK;
+    explicit Entry(int dev) : guard(api, dev)
+    {
+        if (!api)
+            status = MCS_E_HIP;
+        else if (guard.err != hipSuccess)
+            status = fail(MCS_E_HIP, "hipSetDevice(%d): %s", dev,
+                          api->hipGetErrorString(guard.err));
+    }
+    const rt::Api *operator->() const { return api; }
+    operator const rt::Api *() const { return api; }
 };
 
 }  // namespace mcs

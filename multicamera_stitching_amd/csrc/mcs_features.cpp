@@ -13,10 +13,10 @@
 #include "mcs_fparams.h"
 #include "mcs_orb_core.h"
 #include "mcs_ransac_core.h"
+#include "mcs_scratch.h"
 
 namespace {
 
-using mcs::DeviceGuard;
 using mcs::rt::Api;
 using mcs::feat::FeatureKernels;
 using mcs::feat::feature_kernels;
@@ -82,11 +82,8 @@ int workspace(const Api *A, int device, size_t bytes, uint8_t **buf, hipStream_t
 
 int mcs::features_stream_wait(int device, void *event)
 {
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     uint8_t *buf = nullptr;
     hipStream_t s = nullptr;
     int rc = workspace(A, device, 0, &buf, &s);
@@ -185,8 +182,11 @@ int l2_knn2(const Api *A, const FeatureKernels *k, const float *dq, int nq, cons
     const int dimp = (dim + 63) / 64 * 64;
     const size_t n = (size_t)nq + nt;
     const size_t b8 = n * dimp, bi = n * 4, bk = (size_t)nq * 2 * 8;
+    static const char what[] = "l2 knn2";
+    uint32_t hflag = 0;
+    mcs::Scratch sc(A, s);
     uint8_t *buf = nullptr;
-    HIP_TRY(A->hipMalloc((void **)&buf, b8 + 5 * bi + bk + 256));
+    HIP_TRY(sc.dev(&buf, b8 + 5 * bi + bk + 256));
     int8_t *d8 = reinterpret_cast<int8_t *>(buf);
     uint8_t *p = buf + ((b8 + 15) & ~(size_t)15);
     int32_t *norm_i = reinterpret_cast<int32_t *>(p);
@@ -196,9 +196,9 @@ int l2_knn2(const Api *A, const FeatureKernels *k, const float *dq, int nq, cons
     unsigned long long *keys =
         reinterpret_cast<unsigned long long *>(((uintptr_t)(flag + 4) + 15) & ~(uintptr_t)15);
     int rc = MCS_OK;
-    hipError_t e = A->hipMemsetAsync(flag, 0, 4, s);
-    if (e == hipSuccess) e = A->hipMemsetAsync(keys, 0xff, bk, s);
-    for (int side = 0; side < 2 && e == hipSuccess && rc == MCS_OK; side++) {
+    HIP_TRY_AS(what, A->hipMemsetAsync(flag, 0, 4, s));
+    HIP_TRY_AS(what, A->hipMemsetAsync(keys, 0xff, bk, s));
+    for (int side = 0; side < 2; side++) {
         mcs::KL2PrepArgs pa;
         pa.desc = side ? dt : dq;
         pa.n = side ? nt : nq;
@@ -212,6 +212,7 @@ int l2_knn2(const Api *A, const FeatureKernels *k, const float *dq, int nq, cons
         pa.dimp = dimp;
         pa.pad_ = 0;
         if (pa.n > 0) rc = launch(A, k->l2_prep, (pa.n + 3) / 4, 1, 256, &pa, sizeof(pa), s);
+        if (rc) return rc;
     }
     mcs::KL2Args a;
     a.q8 = d8;
@@ -230,20 +231,41 @@ int l2_knn2(const Api *A, const FeatureKernels *k, const float *dq, int nq, cons
     chunks = std::max(1, std::min(chunks, (nt + 255) / 256));
     a.per_chunk = ((nt + chunks - 1) / chunks + 15) / 16 * 16;
     chunks = nt > 0 ? (nt + a.per_chunk - 1) / a.per_chunk : 0;
-    if (e == hipSuccess && rc == MCS_OK && chunks > 0) {
+    if (chunks > 0) {
         rc = launch(A, k->l2_i8, qblocks, chunks, 256, &a, sizeof(a), s);
         if (rc == MCS_OK) rc = launch(A, k->l2_f32, qblocks, chunks, 256, &a, sizeof(a), s);
+        if (rc) return rc;
     }
-    if (e == hipSuccess && rc == MCS_OK)
-        rc = launch(A, k->l2_finalize, (2 * nq + 255) / 256, 1, 256, &a, sizeof(a), s);
-    uint32_t hflag = 0;
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = ws_sync(A, s);
-    (void)A->hipFree(buf);
+    rc = launch(A, k->l2_finalize, (2 * nq + 255) / 256, 1, 256, &a, sizeof(a), s);
     if (rc) return rc;
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "l2 knn2: %s", A->hipGetErrorString(e));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(&hflag, flag, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, sc.synced(ws_sync(A, s)));
     if (exact) *exact = hflag ? 0 : 1;
+    return MCS_OK;
+}
+
+// mcs_match_l2_knn2_host on its stream s, after the checks: upload, match, copy back.
+int l2_host_on_stream(const Api *A, const FeatureKernels *k, hipStream_t s, const float *query,
+                      int n_query, const float *train, int n_train, int dim, int32_t *idx2,
+                      float *dist2, int *exact)
+{
+    static const char what[] = "l2 host path";
+    const size_t qb = (size_t)n_query * dim * 4, tb = (size_t)n_train * dim * 4;
+    const size_t ob = (size_t)n_query * 2 * 4;
+    mcs::Scratch sc(A, s);
+    uint8_t *buf = nullptr;
+    HIP_TRY(sc.dev(&buf, qb + tb + 2 * ob + 64));
+    float *dq = reinterpret_cast<float *>(buf);
+    float *dt = reinterpret_cast<float *>(buf + qb);
+    int32_t *di = reinterpret_cast<int32_t *>(buf + ((qb + tb + 15) & ~(size_t)15));
+    float *dd = reinterpret_cast<float *>(di + (size_t)n_query * 2);
+    HIP_TRY_AS(what, A->hipMemcpyAsync(dq, query, qb, hipMemcpyHostToDevice, s));
+    if (tb) HIP_TRY_AS(what, A->hipMemcpyAsync(dt, train, tb, hipMemcpyHostToDevice, s));
+    const int rc = l2_knn2(A, k, dq, n_query, dt, n_train, dim, di, dd, exact, s);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(idx2, di, ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(dist2, dd, ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, sc.synced(ws_sync(A, s)));
     return MCS_OK;
 }
 
@@ -277,11 +299,8 @@ int mcs_match_hamming_knn2(const uint8_t *d_query, int n_query, const uint8_t *d
     if (n_query == 0) return MCS_OK;
     if (!d_query || (!d_train && n_train) || !d_idx2 || !d_dist2)
         return mcs::fail(MCS_E_INVALID, "NULL buffer");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const FeatureKernels *k = nullptr;
     rc = feature_kernels(A, device, &k);
     if (rc) return rc;
@@ -297,11 +316,8 @@ int mcs_match_hamming_knn2_host(const uint8_t *query, int n_query, const uint8_t
     if (n_query == 0) return MCS_OK;
     if (!query || (!train && n_train) || !idx2 || !dist2)
         return mcs::fail(MCS_E_INVALID, "NULL buffer");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const FeatureKernels *k = nullptr;
     rc = feature_kernels(A, device, &k);
     if (rc) return rc;
@@ -336,11 +352,8 @@ int mcs_match_l2_knn2(const float *d_query, int n_query, const float *d_train, i
     if (n_query == 0) return MCS_OK;
     if (!d_query || (!d_train && n_train) || !d_idx2 || !d_dist2)
         return mcs::fail(MCS_E_INVALID, "NULL buffer");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const FeatureKernels *k = nullptr;
     rc = feature_kernels(A, device, &k);
     if (rc) return rc;
@@ -357,35 +370,15 @@ int mcs_match_l2_knn2_host(const float *query, int n_query, const float *train, 
     if (n_query == 0) return MCS_OK;
     if (!query || (!train && n_train) || !idx2 || !dist2)
         return mcs::fail(MCS_E_INVALID, "NULL buffer");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const FeatureKernels *k = nullptr;
     rc = feature_kernels(A, device, &k);
     if (rc) return rc;
-    const size_t qb = (size_t)n_query * dim * 4, tb = (size_t)n_train * dim * 4;
-    const size_t ob = (size_t)n_query * 2 * 4;
-    uint8_t *buf = nullptr;
-    HIP_TRY(A->hipMalloc((void **)&buf, qb + tb + 2 * ob + 64));
-    float *dq = reinterpret_cast<float *>(buf);
-    float *dt = reinterpret_cast<float *>(buf + qb);
-    int32_t *di = reinterpret_cast<int32_t *>(buf + ((qb + tb + 15) & ~(size_t)15));
-    float *dd = reinterpret_cast<float *>(di + (size_t)n_query * 2);
     hipStream_t s = nullptr;
-    hipError_t e = A->hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = A->hipMemcpyAsync(dq, query, qb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && tb) e = A->hipMemcpyAsync(dt, train, tb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) rc = l2_knn2(A, k, dq, n_query, dt, n_train, dim, di, dd, exact, s);
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(idx2, di, ob, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(dist2, dd, ob, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && s) e = ws_sync(A, s);
-    if (s) (void)A->hipStreamDestroy(s);
-    (void)A->hipFree(buf);
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "l2 host path: %s", A->hipGetErrorString(e));
+    HIP_TRY_AS("l2 host path", A->hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    rc = l2_host_on_stream(A, k, s, query, n_query, train, n_train, dim, idx2, dist2, exact);
+    (void)A->hipStreamDestroy(s);
     return rc;
 }
 
@@ -402,11 +395,8 @@ int mcs_ransac_homography_host(const float *src_xy, const float *dst_xy, int n, 
     if (mask)
         for (int i = 0; i < n; i++) mask[i] = 0;
     if (n < 4) return MCS_OK;   // no model (the reference needs > 4 matches to try)
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const FeatureKernels *k = nullptr;
     int rc = feature_kernels(A, device, &k);
     if (rc) return rc;
@@ -582,11 +572,8 @@ int orb_detect(const uint8_t *image, bool on_device, int w, int h, int channels,
                          "scale=%g threshold=%d", w, h, channels, nfeatures, nlevels,
                          (double)scale_factor, fast_threshold);
     *n_out = 0;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const FeatureKernels *k = nullptr;
     int rc = feature_kernels(A, device, &k);
     if (rc) return rc;

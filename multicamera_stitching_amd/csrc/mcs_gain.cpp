@@ -10,9 +10,9 @@
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#include "mcs_scratch.h"
 
 using namespace mcs::host;
-using mcs::DeviceGuard;
 
 namespace {
 
@@ -38,8 +38,12 @@ int build_overlap(const Api *A, mcs_plan *p, const Kernels *kn, int k, hipStream
     const int64_t np = (int64_t)gw * gh;
     // count[kOvSegs] u32, cursor[kOvSegs] u32, seg_off[kOvSegs] i64
     const size_t cnt_bytes = mcs::kOvSegs * sizeof(uint32_t);
-    uint8_t *d_small = nullptr;
-    HIP_TRY(A->hipMalloc((void **)&d_small, 2 * cnt_bytes + mcs::kOvSegs * sizeof(int64_t)));
+    std::vector<uint32_t> cnt(mcs::kOvSegs, 0);
+    std::vector<int64_t> off(mcs::kOvSegs, 0);
+    std::vector<mcs::OvUnit> units;
+    mcs::Scratch sc(A, s);
+    uint8_t *d_small = nullptr, *d_table = nullptr;
+    HIP_TRY(sc.dev(&d_small, 2 * cnt_bytes + mcs::kOvSegs * sizeof(int64_t)));
     mcs::KOverlapPrepArgs a;
     memset(&a, 0, sizeof(a));
     a.P = p->kp;
@@ -51,65 +55,53 @@ int build_overlap(const Api *A, mcs_plan *p, const Kernels *kn, int k, hipStream
     a.gh = gh;
     a.k = k;
     const unsigned blocks = (unsigned)((np + mcs::kOvPrepThreads - 1) / mcs::kOvPrepThreads);
-    std::vector<uint32_t> cnt(mcs::kOvSegs, 0);
-    std::vector<int64_t> off(mcs::kOvSegs, 0);
-    std::vector<mcs::OvUnit> units;
-    uint8_t *d_table = nullptr;
     int64_t bytes = 0;
-    // (one exit: the small buffer is freed, a half-built table too)
-    const auto run = [&]() -> int {
+    if (np > 0) {   // the count pass
         HIP_TRY(A->hipMemsetAsync(d_small, 0, 2 * cnt_bytes, s));
         a.mode = 0;
-        int r = launch_args(A, kn->overlap_prep[p->fd.interp], blocks, 1, mcs::kOvPrepThreads, 1,
-                            &a, sizeof(a), s);
-        if (r) return r;
+        rc = launch_args(A, kn->overlap_prep[p->fd.interp], blocks, 1, mcs::kOvPrepThreads, 1, &a,
+                         sizeof(a), s);
+        if (rc) return rc;
         HIP_TRY(A->hipMemcpyAsync(cnt.data(), a.count, cnt_bytes, hipMemcpyDeviceToHost, s));
-        HIP_TRY(A->hipStreamSynchronize(s));
-        for (int i = 0; i < n; i++)
-            for (int j = i; j < n; j++) {
-                const int seg = i * MCS_MAX_CAMS + j;
-                const int64_t c = cnt[seg], esz = i == j ? 8 : 16;
-                off[seg] = bytes;
-                for (int64_t e = 0; e < c; e += mcs::kOvUnitEntries) {
-                    mcs::OvUnit u;
-                    u.off = bytes + e * esz;
-                    u.cam_a = i;
-                    u.cam_b = j;
-                    u.n = (int)std::min<int64_t>(mcs::kOvUnitEntries, c - e);
-                    u.pad_ = 0;
-                    units.push_back(u);
-                }
-                bytes += (c * esz + 15) & ~(int64_t)15;
+        HIP_TRY(sc.sync());
+    }
+    for (int i = 0; i < n; i++)
+        for (int j = i; j < n; j++) {
+            const int seg = i * MCS_MAX_CAMS + j;
+            const int64_t c = cnt[seg], esz = i == j ? 8 : 16;
+            off[seg] = bytes;
+            for (int64_t e = 0; e < c; e += mcs::kOvUnitEntries) {
+                mcs::OvUnit u;
+                u.off = bytes + e * esz;
+                u.cam_a = i;
+                u.cam_b = j;
+                u.n = (int)std::min<int64_t>(mcs::kOvUnitEntries, c - e);
+                u.pad_ = 0;
+                units.push_back(u);
             }
-        const int64_t total = bytes + (int64_t)units.size() * sizeof(mcs::OvUnit);
-        if (total > kOverlapTableLimit)
-            return mcs::fail(MCS_E_UNSUPPORTED, "the overlap table at step_log2 %d takes %lld "
-                             "bytes (limit %lld): use a larger step_log2", k, (long long)total,
-                             (long long)kOverlapTableLimit);
-        if (units.empty()) return MCS_OK;   // no camera covers a grid point
-        HIP_TRY(A->hipMalloc((void **)&d_table, (size_t)total));
+            bytes += (c * esz + 15) & ~(int64_t)15;
+        }
+    const int64_t total = bytes + (int64_t)units.size() * sizeof(mcs::OvUnit);
+    if (total > kOverlapTableLimit)
+        return mcs::fail(MCS_E_UNSUPPORTED, "the overlap table at step_log2 %d takes %lld "
+                         "bytes (limit %lld): use a larger step_log2", k, (long long)total,
+                         (long long)kOverlapTableLimit);
+    if (!units.empty()) {   // the fill pass (else: no camera covers a grid point)
+        HIP_TRY(sc.dev(&d_table, (size_t)total));
         HIP_TRY(A->hipMemcpyAsync(d_off, off.data(), mcs::kOvSegs * sizeof(int64_t),
                                   hipMemcpyHostToDevice, s));
         HIP_TRY(A->hipMemcpyAsync(d_table + bytes, units.data(),
                                   units.size() * sizeof(mcs::OvUnit), hipMemcpyHostToDevice, s));
         a.table = d_table;
         a.mode = 1;
-        r = launch_args(A, kn->overlap_prep[p->fd.interp], blocks, 1, mcs::kOvPrepThreads, 1, &a,
-                        sizeof(a), s);
-        if (r) return r;
-        HIP_TRY(A->hipStreamSynchronize(s));
-        return MCS_OK;
-    };
-    rc = np > 0 ? run() : MCS_OK;
-    if (rc) (void)A->hipStreamSynchronize(s);
-    (void)A->hipFree(d_small);
-    if (rc) {
-        if (d_table) (void)A->hipFree(d_table);
-        return rc;
+        rc = launch_args(A, kn->overlap_prep[p->fd.interp], blocks, 1, mcs::kOvPrepThreads, 1, &a,
+                         sizeof(a), s);
+        if (rc) return rc;
+        HIP_TRY(sc.sync());
     }
     mcs_plan::Overlap &ov = p->ov;
     ov.step = k;
-    ov.d_table = d_table;
+    ov.d_table = sc.keep(d_table);   // (the plan's from here on: drop_overlap frees it)
     ov.d_units = d_table ? reinterpret_cast<mcs::OvUnit *>(d_table + bytes) : nullptr;
     ov.n_units = (int)units.size();
     ov.table_bytes = bytes;
@@ -221,11 +213,8 @@ int gain_apply_frames(const mcs_plan *plan, const uint8_t *d_src, uint8_t *d_dst
                       int64_t src_frame_stride, int64_t dst_frame_stride, int n_frames,
                       uint32_t q, const uint16_t *d_q, void *stream)
 {
-    const rt::Api *A = rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, plan->device);
-    if (g.err != hipSuccess)
-        return fail(MCS_E_HIP, "hipSetDevice(%d): %s", plan->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(plan->device);
+    if (A.status) return A.status;
     const Kernels *k = nullptr;
     const int rc = kernels(A, plan->device, &k);
     if (rc) return rc;
@@ -339,11 +328,8 @@ int mcs_gain_apply_device(const uint8_t *d_src, uint8_t *d_dst, int64_t bytes,
     if (!in_place && s0 < d1 && d0 < s1)
         return mcs::fail(MCS_E_INVALID, "src and dst overlap partially (in place: the same "
                          "pointer and frame stride)");
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
     const Kernels *k = nullptr;
     const int rc = kernels(A, device, &k);
     if (rc) return rc;
@@ -372,11 +358,8 @@ int mcs_plan_overlap_stats(mcs_plan *p, const uint8_t *const *d_cams,
     for (int i = 0; i < n * n; i++) N[i] = 0;
     for (size_t i = 0; i < s_count; i++) S[i] = 0;
     if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     hipStream_t s = (hipStream_t)stream;
     int rc = MCS_OK;
     if (!s) {
@@ -438,11 +421,8 @@ int mcs_plan_overlap_stats_direct_async(mcs_plan *p, const uint8_t *const *d_cam
     if (!p || !d_cams || !d_stats) return mcs::fail(MCS_E_INVALID, "NULL plan/d_cams/d_stats");
     const int rc = check_stats_args(p, d_cams, n_frames, step_log2);
     if (rc) return rc;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     return enqueue_direct_stats(A, p, d_cams, cam_frame_stride, n_frames, step_log2,
                                 reinterpret_cast<unsigned long long *>(d_stats),
                                 (hipStream_t)stream);
@@ -461,11 +441,8 @@ int mcs_plan_overlap_stats_direct(mcs_plan *p, const uint8_t *const *d_cams,
     for (size_t i = 0; i < nn; i++) N[i] = 0;
     for (size_t i = 0; i < count - nn; i++) S[i] = 0;
     if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     hipStream_t s = (hipStream_t)stream;
     if (!s) {
         rc = ensure_stream(A, p);
@@ -510,11 +487,8 @@ int mcs_plan_overlap_stats_host(mcs_plan *p, const uint8_t *const *cams, int ste
     need_mask(p->fd, need);
     for (int i = 0; i < p->fd.n_cams; i++)
         if (need[i] && !cams[i]) return mcs::fail(MCS_E_INVALID, "cams[%d] NULL", i);
-    const Api *A = mcs::rt::api();
-    if (!A) return MCS_E_HIP;
-    DeviceGuard g(A, p->device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", p->device, A->hipGetErrorString(g.err));
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
     int rc = ensure_stream(A, p);
     if (rc == MCS_OK) rc = ensure_host_buffers(A, p);
     if (rc) return rc;

@@ -165,9 +165,8 @@ int mcs_group_create(int n_ranks, int rank, const uint8_t *id, int device, mcs_g
     if (!A) return MCS_E_HIP;
     const Rccl *R = rccl(A);
     if (!R) return MCS_E_HIP;
-    mcs::DeviceGuard g(A, device);
-    if (g.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", device, A->hipGetErrorString(g.err));
+    const mcs::Entry on_device(device);
+    if (on_device.status) return on_device.status;
     mcs_group *grp = new (std::nothrow) mcs_group();
     if (!grp) return mcs::fail(MCS_E_NOMEM, "group allocation");
     nccl_id u;
@@ -198,10 +197,8 @@ int mcs_group_gather(mcs_group *g, const uint8_t *d_mosaics, int64_t bytes, uint
     if (!A) return MCS_E_HIP;
     const Rccl *R = rccl(A);
     if (!R) return MCS_E_HIP;
-    mcs::DeviceGuard dg(A, g->device);
-    if (dg.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", g->device,
-                         A->hipGetErrorString(dg.err));
+    const mcs::Entry on_device(g->device);
+    if (on_device.status) return on_device.status;
     hipStream_t s = (hipStream_t)stream;
     // one grouped call: every peer's batch arrives over its own xGMI link concurrently
     RCCL_TRY(R->GroupStart());

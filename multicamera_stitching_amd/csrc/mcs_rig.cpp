@@ -295,9 +295,8 @@ int device_setup(mcs_rig_job *j)
     d.o_pts = btake((size_t)P * K * 4 * sizeof(double));
     d.blob_bytes = b;
     o += b;
-    mcs::DeviceGuard dg(A, j->device);
-    if (dg.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", j->device, A->hipGetErrorString(dg.err));
+    const mcs::Entry on_device(j->device);
+    if (on_device.status) return on_device.status;
     HIP_TRY(A->hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking));
     HIP_TRY(A->hipMalloc((void **)&d.buf, o));
     HIP_TRY(A->hipHostMalloc((void **)&d.host, d.blob_bytes, 0));
@@ -412,9 +411,8 @@ int exposure_buffers(mcs_rig_job *j)
     int rc = MCS_OK;
     const mcs::rt::Api *A = api_for(j->device, &rc);
     if (rc) return rc;
-    mcs::DeviceGuard dg(A, j->device);
-    if (dg.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", j->device, A->hipGetErrorString(dg.err));
+    const mcs::Entry on_device(j->device);
+    if (on_device.status) return on_device.status;
     const size_t bytes = (size_t)j->n_caps * 2 * j->n_cams * j->n_cams * sizeof(int64_t);
     if (!j->d_stats) HIP_TRY(A->hipMalloc((void **)&j->d_stats, bytes));
     if (!j->h_stats) HIP_TRY(A->hipHostMalloc((void **)&j->h_stats, bytes, 0));
@@ -503,9 +501,8 @@ int device_capture(mcs_rig_job *j, bool *overflow)
     }
     RigDevice &d = j->dev;
     const mcs::feat::FeatureKernels *k = nullptr;
-    mcs::DeviceGuard dg(A, j->device);
-    if (dg.err != hipSuccess)
-        return mcs::fail(MCS_E_HIP, "hipSetDevice(%d): %s", j->device, A->hipGetErrorString(dg.err));
+    const mcs::Entry on_device(j->device);
+    if (on_device.status) return on_device.status;
     if ((rc = mcs::feat::feature_kernels(A, j->device, &k)) != MCS_OK) return rc;
     const int C = j->ci, P = j->ci - 1;
     hipStream_t s = d.s;

@@ -16,6 +16,7 @@
 
 #include "mcs_common.h"
 #include "mcs_feat_int.h"
+#include "mcs_scratch.h"
 
 namespace {
 
@@ -193,11 +194,13 @@ int seam_graphcut_device(int device, hipStream_t s, int n_cams, int gw, int gh, 
     }
     int64_t st[5] = {0, 0, 0, 0, 0};
     const auto t0 = std::chrono::steady_clock::now();
+    static const char what[] = "seam max-flow";
+    mcs::Scratch sc(A, s);
     uint8_t *buf = nullptr;
     int32_t *hflag = nullptr;
     const size_t bytes = (size_t)np * (1 + 4 * 4 + 8 + 8 + 4) + 64;
-    HIP_TRY(A->hipMalloc((void **)&buf, bytes));
-    hipError_t e = A->hipHostMalloc((void **)&hflag, 2 * sizeof(int32_t), 0);
+    HIP_TRY(sc.dev(&buf, bytes));
+    HIP_TRY_AS(what, sc.pinned(&hflag, 2));
     mcs::KSeamFlowArgs fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.lab = d_lab;
@@ -226,10 +229,10 @@ int seam_graphcut_device(int device, hipStream_t s, int n_cams, int gw, int gh, 
     auto read_flags = [&]() -> hipError_t {
         hipError_t r = A->hipMemcpyAsync(hflag, fa.flag, 2 * sizeof(int32_t),
                                          hipMemcpyDeviceToHost, s);
-        return r == hipSuccess ? A->hipStreamSynchronize(s) : r;
+        return r == hipSuccess ? sc.sync() : r;
     };
-    for (int a = 0; a < n_cams && e == hipSuccess && rc == MCS_OK; a++)
-        for (int b = a + 1; b < n_cams && e == hipSuccess && rc == MCS_OK; b++) {
+    for (int a = 0; a < n_cams; a++)
+        for (int b = a + 1; b < n_cams; b++) {
             const int i = a * n_cams + b;
             if (bx1[i] < 0) continue;
             fa.a = a;
@@ -241,43 +244,42 @@ int seam_graphcut_device(int device, hipStream_t s, int n_cams, int gw, int gh, 
             const unsigned gy = (unsigned)((fa.bh + kSeamTile - 1) / kSeamTile);
             st[0]++;
             rc = launch(k->seam_init, gx, gy);
-            for (int64_t round = 0; rc == MCS_OK && e == hipSuccess; round++) {
-                if (round >= kMaxRounds) {
-                    rc = mcs::fail(MCS_E_HIP, "seam max-flow: no convergence after %lld rounds",
-                                   (long long)round);
-                    break;
-                }
+            if (rc) return rc;
+            for (int64_t round = 0;; round++) {
+                if (round >= kMaxRounds)
+                    return mcs::fail(MCS_E_HIP, "seam max-flow: no convergence after %lld rounds",
+                                     (long long)round);
                 // global relabel: exact residual distances to the sink
                 st[3]++;
                 rc = launch(k->seam_hinit, gx, gy);
+                if (rc) return rc;
                 // batches of relabel launches, the flag reset before each: the flag read after a
                 // batch is its last launch's, zero only at the fixpoint
                 fa.iters = kRelabelLdsIters;
-                for (;;) {
-                    for (int j = 0; j < kRelabelBatch && e == hipSuccess && rc == MCS_OK; j++) {
-                        e = A->hipMemsetAsync(fa.flag, 0, 2 * sizeof(int32_t), s);
-                        if (e == hipSuccess)
-                            rc = launch(k->seam_relabel_lds, gx, gy);
-                        st[2]++;
+                do {
+                    for (int j = 0; j < kRelabelBatch; j++, st[2]++) {
+                        HIP_TRY_AS(what, A->hipMemsetAsync(fa.flag, 0, 2 * sizeof(int32_t), s));
+                        rc = launch(k->seam_relabel_lds, gx, gy);
+                        if (rc) return rc;
                     }
-                    if (e == hipSuccess && rc == MCS_OK) e = read_flags();
-                    if (e != hipSuccess || rc != MCS_OK || hflag[0] == 0) break;
-                }
-                if (e == hipSuccess && rc == MCS_OK) rc = launch(k->seam_active, gx, gy);
-                if (e == hipSuccess && rc == MCS_OK) e = read_flags();
-                if (e != hipSuccess || rc != MCS_OK || hflag[1] == 0) break;   // maximum preflow
+                    HIP_TRY_AS(what, read_flags());
+                } while (hflag[0] != 0);
+                rc = launch(k->seam_active, gx, gy);
+                if (rc) return rc;
+                HIP_TRY_AS(what, read_flags());
+                if (hflag[1] == 0) break;   // maximum preflow
                 fa.iters = kPushIters;
-                for (int j = 0; j < kPushLaunches && rc == MCS_OK; j++, st[1]++)
+                for (int j = 0; j < kPushLaunches; j++, st[1]++) {
                     rc = launch(k->seam_push, gx, gy);
+                    if (rc) return rc;
+                }
             }
-            if (rc == MCS_OK && e == hipSuccess) rc = launch(k->seam_label, gx, gy);
+            rc = launch(k->seam_label, gx, gy);
+            if (rc) return rc;
         }
-    if (e == hipSuccess && rc == MCS_OK) e = A->hipStreamSynchronize(s);
-    (void)A->hipStreamSynchronize(s);
-    if (hflag) (void)A->hipHostFree(hflag);
-    (void)A->hipFree(buf);
-    if (rc) return rc;
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "seam max-flow: %s", A->hipGetErrorString(e));
+    HIP_TRY_AS(what, sc.sync());
+    // (this function has always synchronised twice here: the runtime sees the calls it saw)
+    HIP_TRY_AS(what, sc.sync());
     st[4] = std::chrono::duration_cast<std::chrono::microseconds>(
                 std::chrono::steady_clock::now() - t0).count();
     if (stats)

@@ -1,6 +1,6 @@
 // Host check of feather on the direct stitch path (built and run by
-// tests/test_direct_feather_native_cpu.py): libmcs's host sources on a stub HIP runtime that
-// records every kernel launch -- name, grid, block and the KDirectArgs block.  A real chain plan
+// tests/test_direct_feather_native_cpu.py): libmcs's host sources on the stub HIP runtime
+// (stub_hip.h), which records every kernel launch -- name, grid, block and the KDirectArgs block.  A real chain plan
 // (mcs_chain_stages + mcs_plan_create, host only) goes through mcs_stitch_direct and
 // mcs_stitch_direct_gained.  Checked: a FEATHER plan launches mcs_direct_feather_c<C>_i<I> over
 // every 128 x 16 tile with grid y = ceil(frames / kDirectFrames); the _g twin only when gains
@@ -18,6 +18,7 @@
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#include "stub_hip.h"
 
 using mcs::host::Api;
 
@@ -28,67 +29,20 @@ struct Launch {
     bool has_args;
 };
 static std::vector<Launch> g_launches;
-static std::map<std::string, uintptr_t> g_handles;
-static std::map<uintptr_t, std::string> g_names;
-static int g_mallocs = 0, g_bad = 0;
+static int g_bad = 0;
 
-static hipError_t s_malloc(void **p, size_t)
+// The launches the stub logged since the log was cleared, into g_launches.
+static void collect_launches()
 {
-    *p = (void *)(uintptr_t)(0x10000 * (uintptr_t)++g_mallocs);
-    return hipSuccess;
-}
-static hipError_t s_free(void *) { return hipSuccess; }
-static hipError_t s_sync(hipStream_t) { return hipSuccess; }
-static hipError_t s_memcpy(void *, const void *, size_t, hipMemcpyKind, hipStream_t)
-{
-    return hipSuccess;
-}
-static hipError_t s_memset(void *, int, size_t, hipStream_t) { return hipSuccess; }
-static hipError_t s_launch(hipFunction_t f, unsigned gx, unsigned gy, unsigned gz, unsigned bx,
-                           unsigned by, unsigned bz, unsigned, hipStream_t, void **, void **cfg)
-{
-    // cfg = {BUFFER_POINTER, args, BUFFER_SIZE, &size, END}
-    Launch l;
-    l.name = g_names[(uintptr_t)f];
-    l.gx = gx, l.gy = gy, l.gz = gz, l.bx = bx, l.by = by, l.bz = bz;
-    const size_t size = *(const size_t *)cfg[3];
-    l.has_args = size == sizeof(mcs::KDirectArgs);
-    if (l.has_args) memcpy(&l.a, cfg[1], sizeof(l.a));
-    g_launches.push_back(l);
-    return hipSuccess;
-}
-static hipError_t s_get_device(int *d)
-{
-    *d = 0;
-    return hipSuccess;
-}
-static hipError_t s_set_device(int) { return hipSuccess; }
-static hipError_t s_device_count(int *n)
-{
-    *n = 1;
-    return hipSuccess;
-}
-static const char *s_errstr(hipError_t) { return "stub error"; }
-static hipError_t s_stream_destroy(hipStream_t) { return hipSuccess; }
-static hipError_t s_event_destroy(hipEvent_t) { return hipSuccess; }
-static hipError_t s_host_free(void *) { return hipSuccess; }
-static hipError_t s_module_unload(hipModule_t) { return hipSuccess; }
-static hipError_t s_graph_exec_destroy(hipGraphExec_t) { return hipSuccess; }
-
-static Api g_api = {};
-
-// what the linked sources need of hip_rt.cpp and mcs_runtime.cpp
-const mcs::rt::Api *mcs::rt::api() { return &g_api; }
-const char *mcs::rt::runtime_name() { return "stub"; }
-int mcs::module_function(const rt::Api *, int, Module, const char *name, hipFunction_t *out)
-{
-    uintptr_t &h = g_handles[name];
-    if (!h) {
-        h = 0x700000 + 16 * g_handles.size();
-        g_names[h] = name;
+    g_launches.clear();
+    for (const stub::Event &e : stub::g.log) {
+        if (e.kind != 'L') continue;
+        Launch l;
+        l.name = e.name;
+        l.gx = e.gx, l.gy = e.gy, l.gz = e.gz, l.bx = e.bx, l.by = e.by, l.bz = e.bz;
+        l.has_args = e.args_as(&l.a);
+        g_launches.push_back(l);
     }
-    *out = (hipFunction_t)h;
-    return MCS_OK;
 }
 
 #define CHECK(cond)                                                                            \
@@ -108,12 +62,14 @@ static uint8_t *const OUT = (uint8_t *)(uintptr_t)0x9000000;
 // A batch through mcs_stitch_direct[_gained]; the launches land in g_launches.
 static int run(mcs_plan *p, int channels, int n_frames, bool gained, const int64_t *strides)
 {
-    g_launches.clear();
+    stub::g.log.clear();
     int w = 0, h = 0, c = 0;
     mcs_plan_out_shape(p, &w, &h, &c);
     const int64_t pitch = (int64_t)w * channels;
-    return (gained ? mcs_stitch_direct_gained : mcs_stitch_direct)(p, CAM, strides, OUT, pitch, 0,
-                                                                   n_frames, nullptr);
+    const int rc = (gained ? mcs_stitch_direct_gained : mcs_stitch_direct)(
+        p, CAM, strides, OUT, pitch, 0, n_frames, nullptr);
+    collect_launches();
+    return rc;
 }
 
 static mcs_plan *make_plan(int channels, int interp)
@@ -135,22 +91,6 @@ static mcs_plan *make_plan(int channels, int interp)
 
 int main()
 {
-    g_api.hipMalloc = s_malloc;
-    g_api.hipFree = s_free;
-    g_api.hipHostFree = s_host_free;
-    g_api.hipStreamSynchronize = s_sync;
-    g_api.hipStreamDestroy = s_stream_destroy;
-    g_api.hipEventDestroy = s_event_destroy;
-    g_api.hipMemcpyAsync = s_memcpy;
-    g_api.hipMemsetAsync = s_memset;
-    g_api.hipModuleLaunchKernel = s_launch;
-    g_api.hipModuleUnload = s_module_unload;
-    g_api.hipGraphExecDestroy = s_graph_exec_destroy;
-    g_api.hipGetErrorString = s_errstr;
-    g_api.hipGetDevice = s_get_device;
-    g_api.hipSetDevice = s_set_device;
-    g_api.hipGetDeviceCount = s_device_count;
-
     for (int channels = 1; channels <= 4; channels += 2)        // 1 and 3
         for (int interp = 0; interp < 2; interp++) {
             mcs_plan *p = make_plan(channels, interp);

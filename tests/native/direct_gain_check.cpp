@@ -1,6 +1,6 @@
 // Host check of the table-free overlap statistics and the rig job's exposure step (built and run
-// by tests/test_direct_gain_native_cpu.py): libmcs's host sources on a stub HIP runtime that
-// records, in order, every kernel launch (name, grid, block, stream, argument block), every
+// by tests/test_direct_gain_native_cpu.py): libmcs's host sources on the stub HIP runtime
+// (stub_hip.h), which records, in order, every kernel launch (name, grid, block, stream, argument block), every
 // stream synchronise, memset and copy.  Checked: mcs_plan_overlap_stats_direct is one memset, one
 // mcs_direct_overlap_c<C>_i<I> launch, one copy back and one synchronise, builds no table and
 // leaves the plan's own alone; the _async form neither allocates nor synchronises; the grid keeps
@@ -21,6 +21,7 @@
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#include "stub_hip.h"
 
 using mcs::host::Api;
 
@@ -35,48 +36,39 @@ struct Event {
     mcs::KDirectOverlapArgs ov;
     mcs::KDirectArgs da;
 };
-static std::vector<Event> g_log;
-static std::mutex g_mu;            // (the rig job's capture runs on a worker thread)
-static std::map<std::string, uintptr_t> g_handles;
-static std::map<uintptr_t, std::string> g_names;
-static int g_mallocs = 0, g_bad = 0;
+static int g_bad = 0;
+static int &g_mallocs = stub::g.mallocs;
 // the rig job's statistics buffers (2 captures x (N, S) of 3 cameras), by their size
 static const size_t kJobStatsBytes = 2 * 2 * 3 * 3 * sizeof(int64_t);
-static void *g_job_dstats = nullptr, *g_job_hstats = nullptr;
+static void *job_dstats() { return stub::device_alloc_of(kJobStatsBytes); }
+static void *job_hstats() { return stub::pinned_alloc_of(kJobStatsBytes); }
 
-static void put(const Event &e)
+// The stub's log since clear_log(), with the argument blocks this program reads.
+static std::vector<Event> g_events;
+static void clear_log()
 {
-    std::lock_guard<std::mutex> lk(g_mu);
-    g_log.push_back(e);
+    std::lock_guard<std::mutex> lk(stub::g.mu);
+    stub::g.log.clear();
+    g_events.clear();
+}
+static const std::vector<Event> &log()
+{
+    std::lock_guard<std::mutex> lk(stub::g.mu);
+    for (size_t i = g_events.size(); i < stub::g.log.size(); i++) {
+        const stub::Event &e = stub::g.log[i];
+        Event o;
+        o.kind = e.kind, o.name = e.name, o.stream = e.stream, o.bytes = e.bytes, o.dst = e.dst;
+        o.gx = e.gx, o.gy = e.gy, o.gz = e.gz, o.bx = e.bx, o.by = e.by, o.bz = e.bz;
+        if (e.kind == 'L') {
+            const bool ov = e.name.rfind("mcs_direct_overlap_", 0) == 0;
+            o.has_ov = ov && e.args_as(&o.ov);
+            o.has_direct = !ov && e.args_as(&o.da);
+        }
+        g_events.push_back(o);
+    }
+    return g_events;
 }
 
-static hipError_t s_malloc(void **p, size_t n)
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    *p = (void *)(uintptr_t)(0x10000000ull * (uintptr_t)++g_mallocs);
-    if (n == kJobStatsBytes) g_job_dstats = *p;
-    return hipSuccess;
-}
-static hipError_t s_free(void *) { return hipSuccess; }
-static hipError_t s_host_malloc(void **p, size_t n, unsigned)
-{
-    *p = calloc(1, n ? n : 1);     // (host code reads the copy-back blobs: zeros)
-    if (n == kJobStatsBytes) g_job_hstats = *p;
-    return *p ? hipSuccess : hipErrorOutOfMemory;
-}
-static hipError_t s_host_free(void *p)
-{
-    free(p);
-    return hipSuccess;
-}
-static hipError_t s_sync(hipStream_t s)
-{
-    Event e;
-    e.kind = 'S';
-    e.stream = s;
-    put(e);
-    return hipSuccess;
-}
 // Statistics a capture of the 3-camera job "measured": camera i's mean 80, 100, 125.
 static const int kJobCams = 3;
 static void fake_stats(int64_t *st)
@@ -90,107 +82,13 @@ static void fake_stats(int64_t *st)
             st[n * n + i * n + j] = c * 3 * mean[i];
         }
 }
-static hipError_t s_memcpy(void *dst, const void *, size_t n, hipMemcpyKind kind, hipStream_t s)
+// the rig job's statistics copy (2 captures x (N, S) of 3 cameras): give the solver overlaps
+static void copy_hook(void *dst, size_t n, hipStream_t)
 {
-    Event e;
-    e.kind = 'C';
-    e.stream = s;
-    e.bytes = n;
-    e.dst = dst;
-    put(e);
-    // the rig job's statistics copy (2 captures x (N, S) of 3 cameras): give the solver overlaps
-    if (kind == hipMemcpyDeviceToHost && dst == g_job_hstats && n == kJobStatsBytes) {
+    if (n == kJobStatsBytes && dst == job_hstats()) {
         fake_stats((int64_t *)dst);
         fake_stats((int64_t *)dst + 2 * kJobCams * kJobCams);
     }
-    return hipSuccess;
-}
-static hipError_t s_memset(void *dst, int, size_t n, hipStream_t s)
-{
-    Event e;
-    e.kind = 'M';
-    e.stream = s;
-    e.bytes = n;
-    e.dst = dst;
-    put(e);
-    return hipSuccess;
-}
-static hipError_t s_launch(hipFunction_t f, unsigned gx, unsigned gy, unsigned gz, unsigned bx,
-                           unsigned by, unsigned bz, unsigned, hipStream_t s, void **, void **cfg)
-{
-    // cfg = {BUFFER_POINTER, args, BUFFER_SIZE, &size, END}
-    Event e;
-    e.kind = 'L';
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        e.name = g_names[(uintptr_t)f];
-    }
-    e.gx = gx, e.gy = gy, e.gz = gz, e.bx = bx, e.by = by, e.bz = bz;
-    e.stream = s;
-    if (cfg) {
-        const size_t size = *(const size_t *)cfg[3];
-        const bool ov = e.name.rfind("mcs_direct_overlap_", 0) == 0;
-        e.has_ov = ov && size == sizeof(mcs::KDirectOverlapArgs);
-        e.has_direct = !ov && size == sizeof(mcs::KDirectArgs);
-        if (e.has_ov) memcpy(&e.ov, cfg[1], sizeof(e.ov));
-        if (e.has_direct) memcpy(&e.da, cfg[1], sizeof(e.da));
-    }
-    put(e);
-    return hipSuccess;
-}
-static hipError_t s_get_device(int *d)
-{
-    *d = 0;
-    return hipSuccess;
-}
-static hipError_t s_set_device(int) { return hipSuccess; }
-static hipError_t s_device_count(int *n)
-{
-    *n = 1;
-    return hipSuccess;
-}
-static const char *s_errstr(hipError_t) { return "stub error"; }
-static hipError_t s_stream_create(hipStream_t *s, unsigned)
-{
-    static uintptr_t next = 0x77000;
-    std::lock_guard<std::mutex> lk(g_mu);
-    *s = (hipStream_t)(next += 0x100);
-    return hipSuccess;
-}
-static hipError_t s_stream_destroy(hipStream_t) { return hipSuccess; }
-static hipError_t s_stream_wait_event(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static hipError_t s_event_destroy(hipEvent_t) { return hipSuccess; }
-static hipError_t s_module_unload(hipModule_t) { return hipSuccess; }
-static hipError_t s_begin_capture(hipStream_t, hipStreamCaptureMode) { return hipSuccess; }
-static hipError_t s_end_capture(hipStream_t, hipGraph_t *g)
-{
-    *g = (hipGraph_t)(uintptr_t)0x6000;
-    return hipSuccess;
-}
-static hipError_t s_graph_instantiate(hipGraphExec_t *x, hipGraph_t, hipGraphNode_t *, char *, size_t)
-{
-    *x = (hipGraphExec_t)(uintptr_t)0x6100;
-    return hipSuccess;
-}
-static hipError_t s_graph_launch(hipGraphExec_t, hipStream_t) { return hipSuccess; }
-static hipError_t s_graph_exec_destroy(hipGraphExec_t) { return hipSuccess; }
-static hipError_t s_graph_destroy(hipGraph_t) { return hipSuccess; }
-
-static Api g_api = {};
-
-// what the linked sources need of hip_rt.cpp and mcs_runtime.cpp
-const mcs::rt::Api *mcs::rt::api() { return &g_api; }
-const char *mcs::rt::runtime_name() { return "stub"; }
-int mcs::module_function(const rt::Api *, int, Module, const char *name, hipFunction_t *out)
-{
-    std::lock_guard<std::mutex> lk(g_mu);
-    uintptr_t &h = g_handles[name];
-    if (!h) {
-        h = 0x700000 + 16 * g_handles.size();
-        g_names[h] = name;
-    }
-    *out = (hipFunction_t)h;
-    return MCS_OK;
 }
 
 #define CHECK(cond)                                                                            \
@@ -241,7 +139,7 @@ static int64_t block_points(int64_t points, unsigned gx)
 static size_t count(char kind, hipStream_t s)
 {
     size_t n = 0;
-    for (const Event &e : g_log) n += e.kind == kind && e.stream == s;
+    for (const Event &e : log()) n += e.kind == kind && e.stream == s;
     return n;
 }
 
@@ -249,7 +147,7 @@ static size_t count(char kind, hipStream_t s)
 static std::string stream_trace()
 {
     std::string t;
-    for (const Event &e : g_log) {
+    for (const Event &e : log()) {
         if (e.stream != STREAM) continue;
         if (e.kind == 'L') t += "L:" + e.name + " ";
         else t += std::string(1, e.kind) + " ";
@@ -259,29 +157,7 @@ static std::string stream_trace()
 
 int main()
 {
-    g_api.hipMalloc = s_malloc;
-    g_api.hipFree = s_free;
-    g_api.hipHostMalloc = s_host_malloc;
-    g_api.hipHostFree = s_host_free;
-    g_api.hipStreamSynchronize = s_sync;
-    g_api.hipStreamCreateWithFlags = s_stream_create;
-    g_api.hipStreamDestroy = s_stream_destroy;
-    g_api.hipStreamWaitEvent = s_stream_wait_event;
-    g_api.hipEventDestroy = s_event_destroy;
-    g_api.hipMemcpyAsync = s_memcpy;
-    g_api.hipMemsetAsync = s_memset;
-    g_api.hipModuleLaunchKernel = s_launch;
-    g_api.hipModuleUnload = s_module_unload;
-    g_api.hipStreamBeginCapture = s_begin_capture;
-    g_api.hipStreamEndCapture = s_end_capture;
-    g_api.hipGraphInstantiate = s_graph_instantiate;
-    g_api.hipGraphLaunch = s_graph_launch;
-    g_api.hipGraphExecDestroy = s_graph_exec_destroy;
-    g_api.hipGraphDestroy = s_graph_destroy;
-    g_api.hipGetErrorString = s_errstr;
-    g_api.hipGetDevice = s_get_device;
-    g_api.hipSetDevice = s_set_device;
-    g_api.hipGetDeviceCount = s_device_count;
+    stub::g.copy_hook = copy_hook;
 
     CHECK(mcs::kDovThreads == 256 && mcs::kOvFrames == 4 && mcs::kDovBlocks == 1024);
     // ---- the grid: enough blocks to fill the chip, more where the partials ask for them
@@ -314,16 +190,16 @@ int main()
             const int ks[3] = {0, 2, 4}, nfs[3] = {1, 4, 5};
             for (int i = 0; i < 3; i++) {
                 const int k = ks[i], nf = nfs[i];
-                g_log.clear();
+                clear_log();
                 const int m0 = g_mallocs;
                 for (int64_t &v : N) v = -1;
                 for (int64_t &v : S) v = -1;
                 CHECK(mcs_plan_overlap_stats_direct(p, CAM, strides, nf, k, N, S, STREAM) == MCS_OK);
                 CHECK(g_mallocs - m0 <= 1);          // (the thread's accumulators, first call)
                 CHECK(stream_trace() == std::string("M L:") + name + " C S ");
-                CHECK(g_log.size() == 4 && p->ov.step == -1 && !p->ov.d_table);
-                if (g_log.size() != 4) continue;
-                const Event &ms = g_log[0], &l = g_log[1], &cp = g_log[2];
+                CHECK(log().size() == 4 && p->ov.step == -1 && !p->ov.d_table);
+                if (log().size() != 4) continue;
+                const Event &ms = log()[0], &l = log()[1], &cp = log()[2];
                 const int gw = (w + (1 << k) - 1) >> k, gh = (h + (1 << k) - 1) >> k;
                 CHECK(ms.bytes == (size_t)(1 + nf) * 9 * 8 && cp.bytes == ms.bytes);
                 CHECK(l.has_ov && l.gx == mcs::dov_blocks((int64_t)gw * gh) &&
@@ -337,38 +213,38 @@ int main()
                 CHECK(N[0] == 0 && S[0] == 0 && S[nf * 9 - 1] == 0);   // (the stub copies nothing)
             }
             // NULL strides: dense frames; NULL stream: the plan's own
-            g_log.clear();
+            clear_log();
             CHECK(mcs_plan_overlap_stats_direct(p, CAM, nullptr, 1, 2, N, S, nullptr) == MCS_OK);
-            CHECK(g_log.size() == 4 && g_log[1].has_ov && g_log[1].ov.P.cam_fstride[2] == fs &&
-                  g_log[1].stream == p->stream && p->stream != nullptr);
+            CHECK(log().size() == 4 && log()[1].has_ov && log()[1].ov.P.cam_fstride[2] == fs &&
+                  log()[1].stream == p->stream && p->stream != nullptr);
 
             // ---- a table the plan has survives the direct call and is not used
             CHECK(mcs_plan_overlap_stats(p, CAM, strides, 1, 2, N, S, STREAM) == MCS_OK);
             // (the stub's counts are zero: the table is empty, its step stands)
             CHECK(p->ov.step == 2);
-            g_log.clear();
+            clear_log();
             CHECK(mcs_plan_overlap_stats_direct(p, CAM, strides, 1, 1, N, S, STREAM) == MCS_OK);
             CHECK(p->ov.step == 2 && stream_trace() == std::string("M L:") + name + " C S ");
 
             // ---- the enqueue-only form: memset + launch, no allocation, no synchronise
-            g_log.clear();
+            clear_log();
             const int m0 = g_mallocs;
             int64_t *const d_stats = (int64_t *)(uintptr_t)0x8000000;
             CHECK(mcs_plan_overlap_stats_direct_async(p, CAM, strides, 5, 2, d_stats, STREAM) ==
                   MCS_OK);
             CHECK(g_mallocs == m0 && stream_trace() == std::string("M L:") + name + " ");
-            CHECK(g_log.size() == 2 && g_log[0].dst == (void *)d_stats &&
-                  g_log[0].bytes == 6 * 9 * 8 && g_log[1].gy == 2 &&
-                  (void *)g_log[1].ov.stats == (void *)d_stats);
+            CHECK(log().size() == 2 && log()[0].dst == (void *)d_stats &&
+                  log()[0].bytes == 6 * 9 * 8 && log()[1].gy == 2 &&
+                  (void *)log()[1].ov.stats == (void *)d_stats);
             // refused arguments launch nothing
-            g_log.clear();
+            clear_log();
             CHECK(mcs_plan_overlap_stats_direct_async(p, CAM, strides, 1, 5, d_stats, STREAM) ==
                   MCS_E_INVALID);
             CHECK(mcs_plan_overlap_stats_direct_async(p, CAM, strides, 0, 2, d_stats, STREAM) ==
                   MCS_E_INVALID);
             CHECK(mcs_plan_overlap_stats_direct(p, CAM, strides, 1, -1, N, S, STREAM) ==
                   MCS_E_INVALID);
-            CHECK(g_log.empty());
+            CHECK(log().empty());
             CHECK(mcs_plan_destroy(p) == MCS_OK);
         }
 
@@ -380,17 +256,17 @@ int main()
             CHECK(mcs_plan_out_shape(p, &w, &h, &c) == MCS_OK && w == 65535 && h == 600);
             const size_t count = 2 * 16 * 16;
             std::vector<int64_t> st(count);
-            g_log.clear();
+            clear_log();
             CHECK(mcs_plan_overlap_stats_direct(p, CAM, nullptr, 1, 0, st.data(), st.data() + 256,
                                                 STREAM) == MCS_OK);
-            CHECK(g_log.size() == 4 && g_log[1].has_ov);
-            if (g_log.size() == 4 && g_log[1].has_ov) {
-                const Event &l = g_log[1];
+            CHECK(log().size() == 4 && log()[1].has_ov);
+            if (log().size() == 4 && log()[1].has_ov) {
+                const Event &l = log()[1];
                 const int64_t np = (int64_t)l.ov.gw * l.ov.gh;
                 CHECK(l.ov.gw == 65535 && l.ov.gh == 600 && l.ov.n_cams == 16 && l.ov.k == 0);
                 CHECK(l.gx == 1024 && l.gy == 1);
                 CHECK(block_points(np, l.gx) * 4 * 255 < (1ll << 32));
-                CHECK(g_log[0].bytes == count * 8);
+                CHECK(log()[0].bytes == count * 8);
             }
             CHECK(mcs_plan_destroy(p) == MCS_OK);
         }
@@ -425,30 +301,30 @@ int main()
             CHECK(mcs_rig_job_gains(j, g, q, &on) == MCS_OK && on == 0 && g[5] == 1.0 && q[0] == 256);
 
             // exposure never set: the parent's launches, no synchronise of the caller's stream
-            g_log.clear();
+            clear_log();
             const std::string off = capture();
             CHECK(off == "L:mcs_direct_feather_c3_i1 L:mcs_direct_feather_c3_i1 ");
             CHECK(count('S', STREAM) == 0 && count('M', STREAM) == 0 && count('C', STREAM) == 0);
-            CHECK(!g_job_dstats && !g_job_hstats);   // (no statistics buffers without exposure)
+            CHECK(!job_dstats() && !job_hstats());   // (no statistics buffers without exposure)
 
             // exposure on
             CHECK(mcs_rig_job_set_exposure(j, 5, 0, 0) == MCS_E_INVALID);
             CHECK(mcs_rig_job_set_exposure(j, 2, 0, 0) == MCS_OK);
-            g_log.clear();
+            clear_log();
             const std::string want_on =
                 "M L:mcs_direct_overlap_c3_i1 M L:mcs_direct_overlap_c3_i1 C S "
                 "L:mcs_direct_feather_c3_i1_g L:mcs_direct_feather_c3_i1_g ";
             CHECK(capture() == want_on);
             std::vector<Event> ev;
-            for (const Event &e : g_log)
+            for (const Event &e : log())
                 if (e.stream == STREAM) ev.push_back(e);
             if (ev.size() == 8) {
                 const size_t per = 2 * n * n * sizeof(int64_t);
-                CHECK(g_job_dstats && ev[0].dst == g_job_dstats && ev[0].bytes == per);
-                CHECK(ev[2].dst == (void *)((uint8_t *)g_job_dstats + per) && ev[2].bytes == per);
+                CHECK(job_dstats() && ev[0].dst == job_dstats() && ev[0].bytes == per);
+                CHECK(ev[2].dst == (void *)((uint8_t *)job_dstats() + per) && ev[2].bytes == per);
                 CHECK(ev[1].has_ov && ev[1].ov.k == 2 && ev[1].ov.n_frames == 1 && ev[1].gy == 1 &&
                       ev[1].ov.P.cams[0] == CAM[0] && ev[3].ov.P.cams[0] == CAM[3]);
-                CHECK(g_job_hstats && ev[4].dst == g_job_hstats && ev[4].bytes == 2 * per);
+                CHECK(job_hstats() && ev[4].dst == job_hstats() && ev[4].bytes == 2 * per);
                 // the solver's gains of the stub's statistics: brighter cameras come down
                 CHECK(mcs_rig_job_gains(j, g, q, &on) == MCS_OK && on == 1);
                 CHECK(g[0] > g[1] && g[1] > g[2] && g[3] == g[0] && g[5] == g[2]);
@@ -463,12 +339,12 @@ int main()
             }
             // a second call reuses the job's buffers
             const int m0 = g_mallocs;
-            g_log.clear();
+            clear_log();
             CHECK(capture() == want_on && g_mallocs == m0);
 
             // disabled again: the parent's launches, identity gains reported
             CHECK(mcs_rig_job_set_exposure(j, -1, 0, 0) == MCS_OK);
-            g_log.clear();
+            clear_log();
             CHECK(capture() == off && count('S', STREAM) == 0);
             CHECK(mcs_rig_job_gains(j, g, q, &on) == MCS_OK && on == 0 && g[0] == 1.0 && q[5] == 256);
             CHECK(mcs_rig_job_destroy(j) == MCS_OK);

@@ -1,8 +1,8 @@
 // Host check of the exposure code (built and run by tests/test_gain_native_cpu.py, also with
 // -fsanitize=address,undefined): mcs_gain_solve_host, the gain quantiser behind mcs_plan_set_gains,
-// the argument checks of mcs_gain_apply_device and the overlap table's life on a stub HIP runtime
-// (hipMalloc hands out fake pointers that are never dereferenced; read-backs keep their zeros, so
-// a table has no entries).  Links mcs_gain.cpp, mcs_prepare.cpp, mcs_sweep_host.cpp and
+// the argument checks of mcs_gain_apply_device and the overlap table's life on the stub HIP runtime
+// (stub_hip.h: hipMalloc hands out fake pointers that are never dereferenced; read-backs keep
+// their zeros, so a table has no entries).  Links mcs_gain.cpp, mcs_prepare.cpp, mcs_sweep_host.cpp and
 // mcs_launch.cpp.  Prints "ok" or the failed checks.
 #include <cmath>
 #include <cstdio>
@@ -10,54 +10,24 @@
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#define STUB_HIP_DEFINE_FAIL   // (mcs_runtime.cpp is not linked)
+#include "stub_hip.h"
 
 using mcs::host::Api;
 
-static std::set<void *> g_live;
-static int g_mallocs = 0, g_bad_free = 0, g_launches = 0, g_bad = 0;
+static int g_bad = 0;
+static auto &g_live = stub::g.live;
+static int &g_bad_free = stub::g.bad_free;
 
-static hipError_t s_malloc(void **p, size_t)
+// Kernel launches so far.
+static int launches()
 {
-    *p = (void *)(uintptr_t)(0x10000 * (uintptr_t)++g_mallocs);
-    g_live.insert(*p);
-    return hipSuccess;
+    int n = 0;
+    for (const stub::Event &e : stub::g.log) n += e.kind == 'L';
+    return n;
 }
-static hipError_t s_free(void *p)
-{
-    if (!g_live.erase(p)) g_bad_free++;
-    return hipSuccess;
-}
-static hipError_t s_sync(hipStream_t) { return hipSuccess; }
-static hipError_t s_memcpy(void *, const void *, size_t, hipMemcpyKind, hipStream_t)
-{
-    return hipSuccess;
-}
-static hipError_t s_memset(void *, int, size_t, hipStream_t) { return hipSuccess; }
-static hipError_t s_launch(hipFunction_t, unsigned, unsigned, unsigned, unsigned, unsigned,
-                           unsigned, unsigned, hipStream_t, void **, void **)
-{
-    g_launches++;
-    return hipSuccess;
-}
-static hipError_t s_get_device(int *d)
-{
-    *d = 0;
-    return hipSuccess;
-}
-static hipError_t s_set_device(int) { return hipSuccess; }
-static const char *s_errstr(hipError_t) { return "stub error"; }
 
-static Api g_api = {};
-
-// what the linked sources need of mcs_runtime.cpp, hip_rt.cpp and mcs_capi.cpp
-int mcs::fail(int code, const char *, ...) { return code; }
-void mcs::clear_error() {}
-int mcs::module_function(const rt::Api *, int, Module, const char *, hipFunction_t *out)
-{
-    *out = nullptr;
-    return MCS_OK;
-}
-const mcs::rt::Api *mcs::rt::api() { return &g_api; }
+// what the linked sources need of mcs_capi.cpp
 int mcs::host::ensure_stream(const Api *, mcs_plan *) { return MCS_OK; }
 int mcs::host::ensure_host_buffers(const Api *, mcs_plan *p)
 {
@@ -77,16 +47,6 @@ static bool near(double a, double b) { return std::fabs(a - b) <= 1e-12 * std::f
 
 int main()
 {
-    g_api.hipMalloc = s_malloc;
-    g_api.hipFree = s_free;
-    g_api.hipStreamSynchronize = s_sync;
-    g_api.hipMemcpyAsync = s_memcpy;
-    g_api.hipMemsetAsync = s_memset;
-    g_api.hipModuleLaunchKernel = s_launch;
-    g_api.hipGetErrorString = s_errstr;
-    g_api.hipGetDevice = s_get_device;
-    g_api.hipSetDevice = s_set_device;
-
     // ---- the solver
     {
         // two cameras, 100 common points, means 100 and 200, alpha 0.01, beta 100:
@@ -153,10 +113,10 @@ int main()
         CHECK(mcs_gain_apply_device(a, a + 8, 16, 0, 0, 1, 256, 0, nullptr) == MCS_E_INVALID);
         CHECK(mcs_gain_apply_device(a, a, 16, 16, 32, 2, 256, 0, nullptr) == MCS_E_INVALID);
         CHECK(mcs_gain_apply_device(a, a + 30, 16, 21, 0, 2, 256, 0, nullptr) == MCS_E_INVALID);
-        CHECK(g_launches == 0);
+        CHECK(launches() == 0);
         CHECK(mcs_gain_apply_device(a, a, 16, 21, 21, 3, 300, 0, nullptr) == MCS_OK);
         CHECK(mcs_gain_apply_device(a, a + 64, 16, 21, 0, 3, 300, 0, nullptr) == MCS_OK);
-        CHECK(g_launches == 2);
+        CHECK(launches() == 2);
     }
 
     // ---- the overlap table on the stub device: built per step, dropped with the plan's lens
@@ -167,18 +127,18 @@ int main()
         CHECK(mcs_plan_overlap_stats(p, cams, nullptr, 2, 2, N, S, nullptr) == MCS_OK);
         CHECK(p->ov.step == 2 && p->ov.n_units == 0 && N[0] == 0 && S[17] == 0);
         CHECK((int)g_live.size() == before);           // (no entries: nothing kept)
-        const int launches = g_launches;
+        const int before_table = launches();
         CHECK(mcs_plan_overlap_stats(p, cams, nullptr, 1, 2, N, S, nullptr) == MCS_OK);
-        CHECK(g_launches == launches);                 // the same step: no second table
+        CHECK(launches() == before_table);                 // the same step: no second table
         CHECK(mcs_plan_overlap_stats(p, cams, nullptr, 1, 0, N, S, nullptr) == MCS_OK);
-        CHECK(p->ov.step == 0 && g_launches == launches + 1);
+        CHECK(p->ov.step == 0 && launches() == before_table + 1);
         CHECK(mcs_plan_overlap_stats_host(p, cams, 3, N, S) == MCS_OK && p->ov.step == 3);
         CHECK(mcs_plan_overlap_stats(p, cams, nullptr, 0, 2, N, S, nullptr) == MCS_E_INVALID);
         CHECK(mcs_plan_overlap_stats(p, cams, nullptr, 1, 5, N, S, nullptr) == MCS_E_INVALID);
         p->single = true;
         CHECK(mcs_plan_overlap_stats(p, cams, nullptr, 1, 2, N, S, nullptr) == MCS_E_UNSUPPORTED);
         p->single = false;
-        mcs::host::drop_overlap(&g_api, p);
+        mcs::host::drop_overlap(stub::api(), p);
         CHECK(p->ov.step == -1 && (int)g_live.size() == before && g_bad_free == 0);
     }
     delete p;

@@ -1,6 +1,6 @@
 // Host check of the fused-gain launch path (built and run by tests/test_gain_fused_native_cpu.py):
-// on a stub HIP runtime that records every kernel launch -- the kernel's name and the KParams at
-// the head of its argument block -- a hand-made prepared plan goes through launch_stitch
+// on the stub HIP runtime (stub_hip.h), which records every kernel launch -- the kernel's name and
+// its argument block, the KParams at its head -- a hand-made prepared plan goes through launch_stitch
 // (mcs_launch.cpp) ungained and gained, in paste, feather and multi-band (levels and band pass)
 // form with both side lists.  Checked: the gained launch takes the _g twin of every kernel that
 // reads source bytes (the multi-band blend has none) and the ungained launch none; the q in the
@@ -16,6 +16,8 @@
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#define STUB_HIP_DEFINE_FAIL   // (mcs_runtime.cpp is not linked)
+#include "stub_hip.h"
 
 using mcs::host::Api;
 
@@ -24,83 +26,26 @@ struct Launch {
     uint16_t q[MCS_MAX_CAMS];
 };
 static std::vector<Launch> g_launches;
-static std::map<std::string, uintptr_t> g_handles;
-static std::map<uintptr_t, std::string> g_names;
-static int g_mallocs = 0, g_bad = 0;
+static int g_bad = 0;
 
-static hipError_t s_malloc(void **p, size_t)
+// The launches the stub logged since the log was cleared, into g_launches: every stitch kernel's
+// argument block starts with its KParams.
+static void collect_launches()
 {
-    *p = (void *)(uintptr_t)(0x10000 * (uintptr_t)++g_mallocs);
-    return hipSuccess;
-}
-static hipError_t s_free(void *) { return hipSuccess; }
-static hipError_t s_sync(hipStream_t) { return hipSuccess; }
-static hipError_t s_memcpy(void *, const void *, size_t, hipMemcpyKind, hipStream_t)
-{
-    return hipSuccess;
-}
-static hipError_t s_memset(void *, int, size_t, hipStream_t) { return hipSuccess; }
-static hipError_t s_launch(hipFunction_t f, unsigned, unsigned, unsigned, unsigned, unsigned,
-                           unsigned, unsigned, hipStream_t, void **, void **cfg)
-{
-    // cfg = {BUFFER_POINTER, args, BUFFER_SIZE, &size, END}; every stitch kernel's block starts
-    // with its KParams
-    Launch l;
-    l.name = g_names[(uintptr_t)f];
-    const size_t size = *(const size_t *)cfg[3];
-    if (size >= sizeof(mcs::KParams))
-        memcpy(l.q, (const char *)cfg[1] + offsetof(mcs::KParams, gain_q), sizeof(l.q));
-    else
-        memset(l.q, 0, sizeof(l.q));
-    g_launches.push_back(l);
-    return hipSuccess;
-}
-static hipError_t s_get_device(int *d)
-{
-    *d = 0;
-    return hipSuccess;
-}
-static hipError_t s_set_device(int) { return hipSuccess; }
-static const char *s_errstr(hipError_t) { return "stub error"; }
-static hipError_t s_event_create(hipEvent_t *e, unsigned)
-{
-    *e = (hipEvent_t)(uintptr_t)(0x500000 + ++g_mallocs);
-    return hipSuccess;
-}
-static hipError_t s_event_record(hipEvent_t, hipStream_t) { return hipSuccess; }
-static hipError_t s_wait_event(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static hipError_t s_stream_create(hipStream_t *s, unsigned)
-{
-    *s = (hipStream_t)(uintptr_t)(0x600000 + ++g_mallocs);
-    return hipSuccess;
-}
-static hipError_t s_stream_create_prio(hipStream_t *s, unsigned f, int)
-{
-    return s_stream_create(s, f);
-}
-static hipError_t s_prio_range(int *least, int *greatest)
-{
-    *least = 0;
-    *greatest = -1;
-    return hipSuccess;
-}
-
-static Api g_api = {};
-
-// what the linked sources need of mcs_runtime.cpp, hip_rt.cpp and mcs_capi.cpp
-int mcs::fail(int code, const char *, ...) { return code; }
-void mcs::clear_error() {}
-int mcs::module_function(const rt::Api *, int, Module, const char *name, hipFunction_t *out)
-{
-    uintptr_t &h = g_handles[name];
-    if (!h) {
-        h = 0x700000 + 16 * g_handles.size();
-        g_names[h] = name;
+    g_launches.clear();
+    for (const stub::Event &e : stub::g.log) {
+        if (e.kind != 'L') continue;
+        Launch l;
+        l.name = e.name;
+        if (e.args.size() >= sizeof(mcs::KParams))
+            memcpy(l.q, e.args.data() + offsetof(mcs::KParams, gain_q), sizeof(l.q));
+        else
+            memset(l.q, 0, sizeof(l.q));
+        g_launches.push_back(l);
     }
-    *out = (hipFunction_t)h;
-    return MCS_OK;
 }
-const mcs::rt::Api *mcs::rt::api() { return &g_api; }
+
+// what the linked sources need of mcs_capi.cpp
 int mcs::host::ensure_stream(const Api *, mcs_plan *) { return MCS_OK; }
 int mcs::host::ensure_host_buffers(const Api *, mcs_plan *) { return MCS_OK; }
 
@@ -126,7 +71,7 @@ static bool has(const char *name)
 // One batch of 3 captures through launch_stitch; the launches land in g_launches.
 static int run(mcs_plan *p, bool gained)
 {
-    g_launches.clear();
+    stub::g.log.clear();
     mcs::KParams kp = p->kp;
     for (int i = 0; i < p->fd.n_cams; i++) {
         kp.cams[i] = (const uint8_t *)(uintptr_t)(0x1000000 * (i + 1));
@@ -135,27 +80,13 @@ static int run(mcs_plan *p, bool gained)
     kp.out = (uint8_t *)(uintptr_t)0x9000000;
     kp.out_pitch = 40 * 3;
     kp.out_fstride = 40 * 3 * 30;
-    return mcs::host::launch_stitch(&g_api, p, kp, 3, nullptr, gained);
+    const int rc = mcs::host::launch_stitch(stub::api(), p, kp, 3, nullptr, gained);
+    collect_launches();
+    return rc;
 }
 
 int main()
 {
-    g_api.hipMalloc = s_malloc;
-    g_api.hipFree = s_free;
-    g_api.hipStreamSynchronize = s_sync;
-    g_api.hipMemcpyAsync = s_memcpy;
-    g_api.hipMemsetAsync = s_memset;
-    g_api.hipModuleLaunchKernel = s_launch;
-    g_api.hipGetErrorString = s_errstr;
-    g_api.hipGetDevice = s_get_device;
-    g_api.hipSetDevice = s_set_device;
-    g_api.hipEventCreateWithFlags = s_event_create;
-    g_api.hipEventRecord = s_event_record;
-    g_api.hipStreamWaitEvent = s_wait_event;
-    g_api.hipStreamCreateWithFlags = s_stream_create;
-    g_api.hipStreamCreateWithPriority = s_stream_create_prio;
-    g_api.hipDeviceGetStreamPriorityRange = s_prio_range;
-
     // a prepared 3-camera plan (cameras 0 and 2 used, camera 1 bypassed) with one tile on each
     // side list; the tables are fake pointers no stub dereferences
     mcs_plan *p = new mcs_plan();

@@ -1,68 +1,20 @@
 // CPU check of the plan's table ownership (built and run by tests/test_plan_tables_cpu.py):
-// mcs_plan::Tables alloc / drop and release_tables / prepare of mcs_prepare.cpp, linked against a
-// stub HIP runtime whose hipMalloc hands out fake pointers (never dereferenced), can fail on the
-// k-th call, and whose hipFree records what it is given.  Prints "ok" or the failed checks.
+// mcs_plan::Tables alloc / drop and release_tables / prepare of mcs_prepare.cpp, linked against
+// the stub HIP runtime (stub_hip.h): hipMalloc hands out fake pointers (never dereferenced) and
+// can fail on the k-th call, hipFree records what it is given.  Prints "ok" or the failed checks.
 #include <cstdio>
 #include <set>
 #include <vector>
 
 #include "mcs_common.h"
 #include "mcs_plan_state.h"
+#define STUB_HIP_DEFINE_FAIL   // (mcs_runtime.cpp is not linked)
+#include "stub_hip.h"
 
 using mcs::host::Api;
 using Tables = mcs_plan::Tables;
 
-// ---- the stub device
-static std::set<void *> g_live;
-static std::vector<void *> g_freed;
-static int g_mallocs = 0, g_fail_at = 0, g_bad_free = 0, g_bad = 0;
-
-static hipError_t s_malloc(void **p, size_t)
-{
-    if (++g_mallocs == g_fail_at) return hipErrorOutOfMemory;
-    *p = (void *)(uintptr_t)(0x10000 * (uintptr_t)g_mallocs);
-    g_live.insert(*p);
-    return hipSuccess;
-}
-static hipError_t s_free(void *p)
-{
-    g_freed.push_back(p);
-    if (!g_live.erase(p)) g_bad_free++;   // never allocated, or freed twice
-    return hipSuccess;
-}
-static hipError_t s_sync(hipStream_t) { return hipSuccess; }
-static hipError_t s_memcpy(void *, const void *, size_t, hipMemcpyKind, hipStream_t)
-{
-    return hipSuccess;   // (read-backs keep the zeros their host buffers start with)
-}
-static hipError_t s_memcpy2d(void *, size_t, const void *, size_t, size_t, size_t, hipMemcpyKind,
-                             hipStream_t)
-{
-    return hipSuccess;
-}
-static hipError_t s_memset(void *, int, size_t, hipStream_t) { return hipSuccess; }
-static hipError_t s_launch(hipFunction_t, unsigned, unsigned, unsigned, unsigned, unsigned,
-                           unsigned, unsigned, hipStream_t, void **, void **)
-{
-    return hipSuccess;
-}
-static const char *s_errstr(hipError_t) { return "stub error"; }
-
-// what mcs_prepare.cpp needs of mcs_runtime.cpp
-int mcs::fail(int code, const char *, ...) { return code; }
-int mcs::module_function(const rt::Api *, int, Module, const char *, hipFunction_t *out)
-{
-    *out = nullptr;
-    return MCS_OK;
-}
-
-static void reset_device(int fail_at)
-{
-    g_live.clear();
-    g_freed.clear();
-    g_mallocs = g_bad_free = 0;
-    g_fail_at = fail_at;
-}
+static int g_bad = 0;
 
 #define CHECK(cond)                                                                            \
     do {                                                                                       \
@@ -112,16 +64,12 @@ constexpr int kFill = 10;
 
 int main()
 {
-    Api api = {};
-    api.hipMalloc = s_malloc;
-    api.hipFree = s_free;
-    api.hipStreamSynchronize = s_sync;
-    api.hipMemcpyAsync = s_memcpy;
-    api.hipMemcpy2DAsync = s_memcpy2d;
-    api.hipMemsetAsync = s_memset;
-    api.hipModuleLaunchKernel = s_launch;
-    api.hipGetErrorString = s_errstr;
-    const Api *A = &api;
+    const Api *A = stub::api();
+    auto &g_live = stub::g.live;
+    auto &g_freed = stub::g.freed;
+    int &g_mallocs = stub::g.mallocs, &g_bad_free = stub::g.bad_free;
+    // (the k-th hipMalloc fails, counted from here; 0: none)
+    const auto reset_device = [](int fail_at) { stub::reset(fail_at, true); };
 
     // (e) a fresh plan: no device allocation, no host memory behind its tables
     reset_device(0);
@@ -139,7 +87,7 @@ int main()
         mcs_plan *p = new mcs_plan();
         p->kp.skip = (const uint8_t *)0x40;
         CHECK(fill(A, p->t) == hipSuccess && g_mallocs == kFill);
-        const std::set<void *> allocated = g_live;
+        const std::set<void *> allocated = stub::live_set();
         const void *dense = p->t.d_dense, *big = p->t.d_big;
         CHECK(p->t.owned.size() == (size_t)kFill && !allocated.count((void *)dense));
         mcs::host::release_tables(A, p);
@@ -202,7 +150,7 @@ int main()
             CHECK(mcs::host::prepare(A, p, nullptr) == MCS_E_HIP);
             CHECK(g_live.empty() && g_bad_free == 0 && g_freed.size() == (size_t)(k - 1));
             CHECK(tables_equal(p->t, Tables{}) && p->t.owned.capacity() == 0);
-            g_fail_at = 0;
+            stub::fail_at(0);
             CHECK(mcs::host::prepare(A, p, nullptr) == MCS_OK && p->t.prepared);
             CHECK(g_live.size() == (size_t)n);
             mcs::host::release_tables(A, p);
