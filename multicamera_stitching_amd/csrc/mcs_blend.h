@@ -298,7 +298,8 @@ __device__ __forceinline__ void feather_tile(const KBlendArgs &a)
 // loop:
 //   mcs_mb_prep_c*_i*   once per plan: per (tile, owner) the source window + folded bilinear
 //                       weights of every level-0 sample (mb_desc), and per tile the seam masks
-//                       m1 (R1 region), m2, and their sums over the owners (the denominators);
+//                       m1 (R1 region), m2, and their sums over the owners (the denominators),
+//                       the blend's work lists and their records (mcs_kparams.h);
 //   mcs_mb_levels_c*    per (tile, owner, 4 captures): samples -> level 0 (LDS) -> separable
 //                       5-tap reduces -> g1 (R1 region, u16) and g2 to a scratch buffer;
 //   mcs_mb_blend_c*     per (tile, capture): B2, R1 = B1 + up(B2), R0 = L0_owner + up(R1) over
@@ -720,12 +721,18 @@ __device__ __forceinline__ void mb_prep(const KMbArgs &a)
         for (int c = 0; c < 4; c++) cls_at[tid][c] = at, at += cls_n[tid][c];
     }
     __syncthreads();
+    // (the lists also stay in LDS: the work records below are built from them)
+    __shared__ uint16_t l_px[kMbTilePx], l_r1[kMbNRX * kMbNRY];
     for (int i = tid; i < kMbTilePx; i += nt)
-        if (px_cls[i] != 255) t_px[atomicAdd(&cls_at[0][px_cls[i]], 1)] = (uint16_t)i;
+        if (px_cls[i] != 255) {
+            const int l = atomicAdd(&cls_at[0][px_cls[i]], 1);
+            t_px[l] = l_px[l] = (uint16_t)i;
+        }
     for (int e = tid; e < kMbNRX * kMbNRY; e += nt)
-        if (need_r1[e])
-            t_r1[atomicAdd(&cls_at[1][mb_cls(G.XR + e % kMbNRX, G.YR + e / kMbNRX)], 1)] =
-                (uint16_t)e;
+        if (need_r1[e]) {
+            const int l = atomicAdd(&cls_at[1][mb_cls(G.XR + e % kMbNRX, G.YR + e / kMbNRX)], 1);
+            t_r1[l] = l_r1[l] = (uint16_t)e;
+        }
     // R1 at a listed entry reads owner j's g1 there and g2 at its level-2 taps where m1_j > 0,
     // and B2 at those taps reads g2_j where m2_j > 0 (positions in the mosaic: reflected, as the
     // blend kernel addresses them)
@@ -752,6 +759,62 @@ __device__ __forceinline__ void mb_prep(const KMbArgs &a)
         }
     }
     __syncthreads();
+    // The blend work records (mcs_kparams.h): per listed pixel and per listed R1 entry every index
+    // mb_blend would otherwise work out per capture, reflection and clamping included, and the R1
+    // entry's mask weights and denominator; the lists' tails padded with inert records.
+    {
+        const int RS = mb_rec_slots(a.slots), RW = mb_r1rec_words(a.slots);
+        uint32_t *rec = a.rec + (int64_t)bt * mb_rec_words(a.slots);
+        uint32_t *rec_r1 = rec + 2 * kMbTilePx;
+        for (int l = tid; l < kMbTilePx; l += nt) {
+            uint32_t w0 = (uint32_t)kMbPxSlotInert << 11, w1 = 0;
+            if (l < n_px) {
+                const int i = l_px[l];
+                const int x = G.X0 + i % kBlendTileW, y = G.Y0 + i / kBlendTileW;
+                const int o = a.owner[(int64_t)y * G.W + x];
+                const int s = o == kBlendNone ? kMbPxSlotNone : __popc(mask & ((1u << o) - 1u));
+                int iy[3], wy[3], ix[3], wx[3];
+                exp_taps<false>(y, G.h1, iy, wy);
+                exp_taps<false>(x, G.w1, ix, wx);
+                w0 = (uint32_t)i | ((uint32_t)s << 11) | ((uint32_t)mb_cls(x, y) << 15);
+                for (int v = 0; v < 3; v++) {
+                    w0 |= (uint32_t)ix2<false>(ix[v], G.XR, kMbNRX) << (17 + 5 * v);
+                    w1 |= (uint32_t)(ix2<false>(iy[v], G.YR, kMbNRY) * kMbNRX) << (10 * v);
+                }
+            }
+            rec[2 * l] = w0;
+            rec[2 * l + 1] = w1;
+        }
+        for (int l = tid; l < kMbRecR1; l += nt) {
+            uint32_t *r = rec_r1 + l * RW;
+            uint32_t w0 = kMbR1Inert, w1 = 0;
+            int p = 0;
+            if (l < n_r1) {
+                const int e = l_r1[l];
+                const int qx = refl(G.XR + e % kMbNRX, G.w1), qy = refl(G.YR + e / kMbNRX, G.h1);
+                int iy[3], wy[3], ix[3], wx[3];
+                exp_taps<false>(qy, G.h2, iy, wy);
+                exp_taps<false>(qx, G.w2, ix, wx);
+                const int py = ix2<false>(qy, G.YR, kMbNRY), px = ix2<false>(qx, G.XR, kMbNRX);
+                p = (py + kMbRS) * kMbN1X + px + kMbRS;   // (m1 is held over the level-1 array)
+                int d = 0;
+                for (int j = 0; j < ns; j++) d += m1[j][p];
+                w0 = (uint32_t)e | ((uint32_t)(py * kMbNRX + px) << 10) |
+                     ((uint32_t)mb_cls(qx, qy) << 20) | ((uint32_t)d << 22);
+                for (int v = 0; v < 3; v++) {
+                    w1 |= (uint32_t)ix2<false>(iy[v], G.Y2, kMbN2Y) << (5 * v);
+                    w1 |= (uint32_t)ix2<false>(ix[v], G.X2, kMbN2X) << (15 + 4 * v);
+                }
+            }
+            r[0] = w0;
+            r[1] = w1;
+            for (int j = 0; j < RS; j += 2) {
+                const uint32_t ma = l < n_r1 && j < ns ? (uint32_t)m1[j][p] : 0u;
+                const uint32_t mb = l < n_r1 && j + 1 < ns ? (uint32_t)m1[j + 1][p] : 0u;
+                r[2 + j / 2] = ma | (mb << 16);
+            }
+        }
+    }
     // Column ranges of the level arrays the mixed pixels depend on (interior tiles; mosaic-border
     // tiles keep the full arrays): R1 entries -> their level-2 taps -> the level-1 entries the R1
     // region and those taps reduce from -> the level-0 samples.  mb_levels computes only these.
@@ -1773,45 +1836,62 @@ struct MbBlLds {
 };
 
 constexpr int kMbPQ = kMbTilePx / kMbBlThreads;   // tile pixels per thread
-template <int CN>
-struct MbPix {
-    int i[kMbPQ];            // the thread's mixed pixels (tile index, -1: none)
-    int own[kMbPQ];          // owner slot of each of the thread's pixels (kBlendNone: none)
-    uint32_t v[kMbPQ];       // its owner sample (the stitch kernel's output), channel k in byte k
+static_assert(kMbN2X * kMbN2Y <= kMbBlThreads, "mb_blend: one level-2 entry per thread");
+
+// What a blend thread holds from the block's one round of loads: its work records (mcs_kparams.h;
+// iterations past a list's end hold inert records), its pixels' owner samples, and the B2
+// operands of level-2 entry `tid`.
+template <int CN, int S>
+struct MbWork {
+    uint2 px[kMbPQ];                              // pixel records
+    uint32_t v[kMbPQ];       // their owner samples (the stitch kernel's output), channel k in byte k
+    uint32_t r1[kMbR1Iters][mb_r1rec_words(S)];   // R1 records
+    int32_t m2[S], d2;                            // m2[j][tid], d2[tid]
 };
 
-template <int CN, int S, bool IN>
+// Expand weights of a parity class along one axis (exp_taps): odd -> 4 4 (0), even -> 1 6 1.
+__device__ __forceinline__ void mb_cls_wt(bool odd, int *wt)
+{
+    wt[0] = odd ? 4 : 1, wt[1] = odd ? 4 : 6, wt[2] = odd ? 0 : 1;
+}
+
+// m1 of owner slot j from an R1 record's packed words (16 bits a slot): a shift by j, never a
+// register array indexed by j.
+template <int S>
+__device__ __forceinline__ uint32_t mb_rec_m1(const uint32_t *w, int j)
+{
+    if constexpr (S == 2) {
+        return (w[2] >> (j * 16)) & 0xffffu;
+    } else if constexpr (S == 4) {
+        return (uint32_t)(((uint64_t)w[2] | ((uint64_t)w[3] << 32)) >> (j * 16)) & 0xffffu;
+    } else {
+        const uint64_t lo = (uint64_t)w[2] | ((uint64_t)w[3] << 32);
+        const uint64_t hi = (uint64_t)w[4] | ((uint64_t)w[5] << 32);
+        return (uint32_t)((j < 4 ? lo : hi) >> ((j & 3) * 16)) & 0xffffu;
+    }
+}
+
+template <int CN, int S>
 __device__ __forceinline__ void mb_blend_tile(const KMbArgs &a, const MbGeo &G, MbBlLds<CN, S> &L,
-                                              const MbPix<CN> &px, uint32_t mask, int ns, int f,
-                                              int bt)
+                                              const MbWork<CN, S> &wk, int ns, int n_r1, int f)
 {
     const KParams &P = a.P;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int32_t *tab = a.tab + (int64_t)bt * mb_tab_words(a.slots);
-    const int32_t *t_m1 = tab, *t_m2 = tab + a.slots * kMbNRX * kMbNRY;
-    const int32_t *t_d1 = t_m2 + a.slots * kMbN2X * kMbN2Y, *t_d2 = t_d1 + kMbNRX * kMbNRY;
-    // (24-bit multiplies: full-rate v_mul_u32_u24 instead of quarter-rate v_mul_lo_u32)
-    auto i2 = [&](int cx, int cy) {
-        return (int)__umul24((unsigned)ix2<IN>(cy, G.Y2, kMbN2Y), kMbN2X) + ix2<IN>(cx, G.X2, kMbN2X);
-    };
-    auto ir = [&](int cx, int cy) {   // the R1 region (g1, m1, d1, r1)
-        return (int)__umul24((unsigned)ix2<IN>(cy, G.YR, kMbNRY), kMbNRX) + ix2<IN>(cx, G.XR, kMbNRX);
-    };
-    const int n_r1 = t_d2[kMbN2X * kMbN2Y + 1];
-    const uint16_t *t_r1 =
-        reinterpret_cast<const uint16_t *>(t_d2 + kMbN2X * kMbN2Y + kMbTabCounts) + kMbTilePx;
+    const int tid = threadIdx.x;
     // B2 = sum m2 g2 / (sum m2 * 65536)
-    for (int e = tid; e < kMbN2X * kMbN2Y; e += nt) {
+    if (tid < kMbN2X * kMbN2Y) {
+        const int e = tid;
         // (integer sums in double: every product < 2^41, every sum < 2^43 -- exact)
         double num[CN];
 #pragma unroll
         for (int k = 0; k < CN; k++) num[k] = 0.0;
-        for (int j = 0; j < ns; j++) {
-            const double m = (double)t_m2[__umul24((unsigned)j, kMbN2X * kMbN2Y) + e];
+#pragma unroll
+        for (int j = 0; j < S; j++) {
+            if (j >= ns) break;
+            const double m = (double)wk.m2[j];
 #pragma unroll
             for (int k = 0; k < CN; k++) num[k] += m * (double)L.g2[j][k][e];
         }
-        const int den = t_d2[e];
+        const int den = wk.d2;
 #pragma unroll
         for (int k = 0; k < CN; k++)
             L.b2[k][e] = den ? num[k] / ((double)den * 65536.0) : 0.0;
@@ -1820,23 +1900,27 @@ __device__ __forceinline__ void mb_blend_tile(const KMbArgs &a, const MbGeo &G, 
     // R1 = B1 + up(B2), B1 = sum m1 (16384 g1 - E(g2)) / (sum m1 * 4194304)
     // (the list is grouped by parity class, mb_prep: the zero-weight third taps of odd
     // coordinates are skipped by whole waves)
-    for (int l = tid; l < n_r1; l += nt) {
-        const int e = t_r1[l];
-        const int ey = div_small<kMbNRX>(e), ex = e - (int)__umul24((unsigned)ey, kMbNRX);
-        const int qx = rf<IN>(G.XR + ex, G.w1), qy = rf<IN>(G.YR + ey, G.h1);
-        int iy[3], wy[3], ix[3], wx[3];
-        exp_taps<IN>(qy, G.h2, iy, wy);
-        exp_taps<IN>(qx, G.w2, ix, wx);
-        const bool y3 = wy[2] != 0, x3 = wx[2] != 0;
+#pragma unroll
+    for (int it = 0; it < kMbR1Iters; it++) {
+        if (it * kMbBlThreads >= n_r1) break;   // (uniform)
+        const uint32_t *rw = wk.r1[it];
+        const int e = (int)(rw[0] & 1023u);
+        if (e == kMbR1Inert) continue;
+        const int p1 = (int)((rw[0] >> 10) & 1023u), cls = (int)((rw[0] >> 20) & 3u);
+        int wy[3], wx[3];
+        mb_cls_wt((cls & 2) != 0, wy);
+        mb_cls_wt((cls & 1) != 0, wx);
+        const bool y3 = (cls & 2) == 0, x3 = (cls & 1) == 0;
         int tp[9], tw[9];
 #pragma unroll
         for (int u = 0; u < 3; u++)
 #pragma unroll
             for (int v = 0; v < 3; v++) {
-                tp[3 * u + v] = i2(ix[v], iy[u]);
+                // (24-bit multiply: full-rate v_mul_u32_u24 instead of quarter-rate v_mul_lo_u32)
+                tp[3 * u + v] = (int)__umul24((rw[1] >> (5 * u)) & 31u, kMbN2X) +
+                                (int)((rw[1] >> (15 + 4 * v)) & 15u);
                 tw[3 * u + v] = wy[u] * wx[v];
             }
-        const int p1 = ir(qx, qy);
         // (integer sums in double: every product < 2^39, every sum < 2^41 -- exact)
         double num[CN];
 #pragma unroll
@@ -1853,11 +1937,11 @@ __device__ __forceinline__ void mb_blend_tile(const KMbArgs &a, const MbGeo &G, 
                     e2[k] += (int)__umul24((unsigned)tw[t], (unsigned)L.g2[j][k][tp[t]]);
             }
             const uint2 g1 = L.g1[j][p1];
-            const double m = (double)t_m1[__umul24((unsigned)j, kMbNRX * kMbNRY) + p1];
+            const double m = (double)mb_rec_m1<S>(rw, j);
 #pragma unroll
             for (int k = 0; k < CN; k++) num[k] += m * (double)(16384 * ch16(g1, k) - e2[k]);
         }
-        const int den = t_d1[p1];
+        const int den = (int)(rw[0] >> 22);
         double acc[CN];
 #pragma unroll
         for (int k = 0; k < CN; k++) acc[k] = 0.0;
@@ -1879,22 +1963,23 @@ __device__ __forceinline__ void mb_blend_tile(const KMbArgs &a, const MbGeo &G, 
     // owner sample already in the mosaic
 #pragma unroll
     for (int q = 0; q < kMbPQ; q++) {
-        const int i = px.i[q];
-        if (i < 0) continue;
+        const uint2 pr = wk.px[q];
+        const int s = (int)((pr.x >> 11) & 15u);
+        if (s == kMbPxSlotInert) continue;
+        const int i = (int)(pr.x & 2047u);
         const int x = G.X0 + (i % kBlendTileW), y = G.Y0 + i / kBlendTileW;
         // (global address space: the stores cannot alias the LDS arrays read by later pixels)
         typedef __attribute__((address_space(1))) uint8_t gu8;
         gu8 *po = (gu8 *)(P.out + (int64_t)f * P.out_fstride + (int64_t)y * P.out_pitch + x * CN);
-        const int o = px.own[q];
-        if (o == kBlendNone) {
+        if (s == kMbPxSlotNone) {
 #pragma unroll
             for (int k = 0; k < CN; k++) po[k] = 0;
             continue;
         }
-        const int s = __popc(mask & ((1u << o) - 1u));
-        int iy[3], wy[3], ix[3], wx[3];
-        exp_taps<IN>(y, G.h1, iy, wy);
-        exp_taps<IN>(x, G.w1, ix, wx);
+        const int cls = (int)((pr.x >> 15) & 3u);
+        int wy[3], wx[3];
+        mb_cls_wt((cls & 2) != 0, wy);
+        mb_cls_wt((cls & 1) != 0, wx);
         int e1[CN];   // <= 64 * 256 * 255: exact in int32
         double acc[CN];
 #pragma unroll
@@ -1908,7 +1993,8 @@ __device__ __forceinline__ void mb_blend_tile(const KMbArgs &a, const MbGeo &G, 
 #pragma unroll
             for (int v = 0; v < 3; v++) {
                 if (v == 2 && wx[2] == 0) break;
-                const int p = ir(ix[v], iy[u]), wt = wy[u] * wx[v];
+                const int p = (int)(((pr.y >> (10 * u)) & 1023u) + ((pr.x >> (17 + 5 * v)) & 31u));
+                const int wt = wy[u] * wx[v];
                 const uint2 g1 = L.g1[s][p];
                 const double wd = (double)wt;
 #pragma unroll
@@ -1920,7 +2006,7 @@ __device__ __forceinline__ void mb_blend_tile(const KMbArgs &a, const MbGeo &G, 
         }
 #pragma unroll
         for (int k = 0; k < CN; k++) {
-            const int l0 = 16384 * (int)((px.v[q] >> (8 * k)) & 0xffu) - e1[k];
+            const int l0 = 16384 * (int)((wk.v[q] >> (8 * k)) & 0xffu) - e1[k];
             const double r0 = (double)l0 / 16384.0 + acc[k] / 64.0;
             const double vf = floor(r0 + 0.5);
             po[k] = (uint8_t)(vf < 0.0 ? 0.0 : (vf > 255.0 ? 255.0 : vf));
@@ -1939,74 +2025,105 @@ __device__ __forceinline__ void mb_blend(const KMbArgs &a, MbBlLds<CN, S> &L)
     int ux, fl;
     if (!xcd_unit(a.n_list, a.nf, ux, fl)) return;   // (block-uniform, before any barrier)
     const int bt = a.list0 + ux, tid = threadIdx.x;
+    // Every global read of the block in one round.  What depends on nothing but the list index
+    // and the thread goes first: the first iteration of both record lists and the B2 operands of
+    // level-2 entry `tid` (the tables hold zeros for the slots past the tile's owners).
+    typedef __attribute__((address_space(1))) const uint32_t cgu32;
+    constexpr int RW = mb_r1rec_words(S);
+    const cgu32 *rec = (const cgu32 *)a.rec + (int64_t)bt * mb_rec_words(S);
+    const cgu2 *rec_px = (const cgu2 *)rec;
+    const cgu32 *rec_r1 = rec + 2 * kMbTilePx;
+    const cgi32 *tab = (const cgi32 *)a.tab + (int64_t)bt * mb_tab_words(a.slots);
+    const cgi32 *t_m2 = tab + a.slots * kMbNRX * kMbNRY;
+    const cgi32 *t_d2 = t_m2 + a.slots * kMbN2X * kMbN2Y + kMbNRX * kMbNRY;
+    MbWork<CN, S> wk;
+    wk.px[0] = rec_px[tid];
+#pragma unroll
+    for (int w = 0; w < RW; w++) wk.r1[0][w] = rec_r1[tid * RW + w];
+    {
+        const int e = min(tid, kMbN2X * kMbN2Y - 1);
+#pragma unroll
+        for (int j = 0; j < S; j++)   // (a slot past the table's: row 0 again, never used)
+            wk.m2[j] = t_m2[(j < a.slots ? j : 0) * (kMbN2X * kMbN2Y) + e];
+        wk.d2 = t_d2[e];
+    }
+    // The list entry and the counts (uniform loads) say how far the lists run: a tile's later
+    // iterations are whole iterations of records too, loaded only where the list reaches them.
     const uint32_t mask = (uint32_t)a.list[2 + 2 * bt];
     const int ns = __popc(mask), f = a.f0 + fl;
     const MbGeo G = mb_geo(P, a.list[1 + 2 * bt]);
-    // every global read of the block issued up front (one memory round trip): the tile pixels'
-    // owners and owner samples, and the owners' level scratch
-    MbPix<CN> px;
-    int n_px;
-    {
-        const cgi32 *tc = (const cgi32 *)a.tab + (int64_t)bt * mb_tab_words(a.slots) +
-                          a.slots * (kMbNRX * kMbNRY + kMbN2X * kMbN2Y) + kMbNRX * kMbNRY +
-                          kMbN2X * kMbN2Y;
-        typedef __attribute__((address_space(1))) const uint16_t cgu16;
-        n_px = tc[0];
-        const cgu16 *lp = (const cgu16 *)(tc + kMbTabCounts);
-#pragma unroll
-        for (int q = 0; q < kMbPQ; q++) {
-            const int l = tid + q * kMbBlThreads;
-            px.i[q] = l < n_px ? (int)lp[l] : -1;
-        }
-    }
+    const cgi32 *tc = t_d2 + kMbN2X * kMbN2Y;
+    const int n_px = tc[0], n_r1 = tc[1];
     if (n_px == 0) return;   // uniform: no mixed pixel in this tile (before any barrier)
 #pragma unroll
-    for (int q = 0; q < kMbPQ; q++) {
-        const int i = px.i[q];
-        const int x = G.X0 + (i % kBlendTileW), y = G.Y0 + i / kBlendTileW;
-        px.own[q] = kBlendNone;
-        px.v[q] = 0;
-        if (i >= 0) {
-            px.own[q] = ((cgu8 *)a.owner)[(int64_t)y * G.W + x];
-            const cgu8 *po = (const cgu8 *)(P.out + (int64_t)f * P.out_fstride +
-                                            (int64_t)y * P.out_pitch + x * CN);
+    for (int q = 1; q < kMbPQ; q++) {
+        wk.px[q] = make_uint2((uint32_t)kMbPxSlotInert << 11, 0u);
+        if (q * kMbBlThreads < n_px) wk.px[q] = rec_px[tid + q * kMbBlThreads];
+    }
 #pragma unroll
-            for (int k = 0; k < CN; k++) px.v[q] |= (uint32_t)po[k] << (8 * k);
+    for (int it = 1; it < kMbR1Iters; it++) {
+#pragma unroll
+        for (int w = 0; w < RW; w++) wk.r1[it][w] = w == 0 ? (uint32_t)kMbR1Inert : 0u;
+        if (it * kMbBlThreads < n_r1) {
+#pragma unroll
+            for (int w = 0; w < RW; w++) wk.r1[it][w] = rec_r1[(tid + it * kMbBlThreads) * RW + w];
         }
     }
     constexpr int N1 = (kMbNRX * kMbNRY + kMbBlThreads - 1) / kMbBlThreads;
     constexpr int N2 = (kMbN2X * kMbN2Y * CN + kMbBlThreads - 1) / kMbBlThreads;
-    uint2 r1[S][N1];
-    int32_t r2[S][N2];
+    // (the eight-owner kernels stage four owners at a time: all eight beside the records would
+    // pass 128 registers)
+    constexpr int SG = S > 4 ? 4 : S;
 #pragma unroll
-    for (int j = 0; j < S; j++) {
-        if (j >= ns) break;
-        const int64_t job = ((int64_t)bt * a.slots + j) * a.chunk + fl;
-        const cgu2 *s1 = (const cgu2 *)a.g1 + job * (kMbNRX * kMbNRY);
-        const cgi32 *s2 = (const cgi32 *)a.g2 + job * (kMbN2X * kMbN2Y * CN);
+    for (int j0 = 0; j0 < S; j0 += SG) {
+        if (j0 >= ns) break;
+        uint2 r1[SG][N1];
+        int32_t r2[SG][N2];
 #pragma unroll
-        for (int q = 0; q < N1; q++)
-            r1[j][q] = s1[min(tid + q * kMbBlThreads, kMbNRX * kMbNRY - 1)];
+        for (int j = 0; j < SG; j++) {
+            if (j0 + j >= ns) break;
+            const int64_t job = ((int64_t)bt * a.slots + j0 + j) * a.chunk + fl;
+            const cgu2 *s1 = (const cgu2 *)a.g1 + job * (kMbNRX * kMbNRY);
+            const cgi32 *s2 = (const cgi32 *)a.g2 + job * (kMbN2X * kMbN2Y * CN);
 #pragma unroll
-        for (int q = 0; q < N2; q++)
-            r2[j][q] = s2[min(tid + q * kMbBlThreads, kMbN2X * kMbN2Y * CN - 1)];
-    }
-    // (the scratch holds an entry's channels together, mb_g2_at; LDS is channel-planar)
+            for (int q = 0; q < N1; q++)
+                r1[j][q] = s1[min(tid + q * kMbBlThreads, kMbNRX * kMbNRY - 1)];
 #pragma unroll
-    for (int j = 0; j < S; j++) {
-        if (j >= ns) break;
+            for (int q = 0; q < N2; q++)
+                r2[j][q] = s2[min(tid + q * kMbBlThreads, kMbN2X * kMbN2Y * CN - 1)];
+        }
+        // (the scratch holds an entry's channels together, mb_g2_at; LDS is channel-planar)
 #pragma unroll
-        for (int q = 0; q < N1; q++)
-            if (tid + q * kMbBlThreads < kMbNRX * kMbNRY) L.g1[j][tid + q * kMbBlThreads] = r1[j][q];
+        for (int j = 0; j < SG; j++) {
+            if (j0 + j >= ns) break;
 #pragma unroll
-        for (int q = 0; q < N2; q++) {
-            const int e = tid + q * kMbBlThreads;
-            if (e < kMbN2X * kMbN2Y * CN) L.g2[j][e % CN][e / CN] = r2[j][q];
+            for (int q = 0; q < N1; q++)
+                if (tid + q * kMbBlThreads < kMbNRX * kMbNRY)
+                    L.g1[j0 + j][tid + q * kMbBlThreads] = r1[j][q];
+#pragma unroll
+            for (int q = 0; q < N2; q++) {
+                const int e = tid + q * kMbBlThreads;
+                if (e < kMbN2X * kMbN2Y * CN) L.g2[j0 + j][e % CN][e / CN] = r2[j][q];
+            }
         }
     }
+    // the owner samples of the thread's pixels: the one read that needs a record (first used in
+    // R0, behind both barriers)
+#pragma unroll
+    for (int q = 0; q < kMbPQ; q++) {
+        const uint32_t w = wk.px[q].x;
+        const int i = (int)(w & 2047u);
+        const int x = G.X0 + (i % kBlendTileW), y = G.Y0 + i / kBlendTileW;
+        // (unconditional: an inert record names tile pixel 0, which lies inside the mosaic)
+        const cgu8 *po = (const cgu8 *)(P.out + (int64_t)f * P.out_fstride +
+                                        (int64_t)y * P.out_pitch + x * CN);
+        wk.v[q] = 0;
+#pragma unroll
+        for (int k = 0; k < CN; k++) wk.v[q] |= (uint32_t)po[k] << (8 * k);
+    }
     __syncthreads();
-    if (G.interior) mb_blend_tile<CN, S, true>(a, G, L, px, mask, ns, f, bt);
-    else mb_blend_tile<CN, S, false>(a, G, L, px, mask, ns, f, bt);
+    // (the records hold reflected and clamped indices: interior and edge tiles run the same code)
+    mb_blend_tile<CN, S>(a, G, L, wk, ns, n_r1, f);
 }
 
 }  // namespace mcs

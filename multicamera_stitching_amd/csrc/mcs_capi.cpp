@@ -854,7 +854,9 @@ int mcs_plan_stats(const mcs_plan *p, int64_t *stats, int n)
     for (int c = 0; c < MCS_MAX_CAMS; c++) lens_cams += (p->kp.lens_mask >> c) & 1u;
     const int64_t v[21] = {p->t.prepared ? 1 : 0, tiles, tiles - p->t.n_fallback, p->t.n_fallback,
                            tiles * (int64_t)(sizeof(mcs::TileHdr) +
-                                             mcs::kTilePx * (mcs::kDescWords + 1) * 4),
+                                             mcs::kTilePx * (mcs::kDescWords + 1) * 4) +
+                               (p->t.d_mbrec ? (int64_t)p->t.n_blend *
+                                                   mcs::mb_rec_words(p->t.mb_slots) * 4 : 0),
                            p->blend, p->t.n_blend, p->t.mb_slots, p->t.n_degraded, p->t.n_bands,
                            p->t.n_bands_lds, p->t.n_big, p->t.mb_mixed_px, p->t.mb_r1,
                            p->t.dma_bytes, p->t.box_bytes, p->t.n_strips, p->t.sw_px,

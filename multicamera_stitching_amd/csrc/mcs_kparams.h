@@ -225,6 +225,35 @@ constexpr int mb_tab_words(int slots)
     return slots * (kMbNRX * kMbNRY + kMbN2X * kMbN2Y) + kMbNRX * kMbNRY + kMbN2X * kMbN2Y +
            kMbTabLists;
 }
+// Blend work records (mb_prep -> mb_blend), per listed tile: what the blend block needs of its
+// two work lists with every index already worked out -- constants of the tile, the same for every
+// capture.  Record l of a list belongs to thread l % kMbBlThreads, iteration l / kMbBlThreads;
+// both lists are padded with inert records to whole iterations, so a record's address depends on
+// (list index, thread, iteration) alone.
+//   pixel record (2 words), one per listed mixed pixel, in the list's parity-class order:
+//     .x = tile pixel | owner's local slot << 11 | parity class << 15 | the three R1-region
+//          columns of its expand taps << 17, 22, 27 (reflected and clamped, as mb_blend reads them)
+//     .y = the three R1-region rows of its taps, times kMbNRX, << 0, 10, 20
+//   R1 record (2 + slots / 2 words), one per listed R1 entry, in the list's order:
+//     word 0 = e | p1 << 10 | parity class << 20 | d1[p1] << 22
+//     word 1 = the three level-2 rows of its taps << 0, 5, 10, the three columns << 15, 19, 23
+//     then m1[j][p1] of the tile's owner slots, 16 bits each (a mask weight is at most 256)
+// with the slot dimension rounded to the blend kernel's (2, 4 or 8).
+constexpr int kMbPxSlotInert = 15;   // pixel record: padding (no pixel)
+constexpr int kMbPxSlotNone = 14;    // pixel record: no camera covers the pixel
+constexpr int kMbR1Inert = 1023;     // R1 record, field e: padding (no entry)
+constexpr int kMbR1Iters = (kMbNRX * kMbNRY + kMbBlThreads - 1) / kMbBlThreads;
+constexpr int kMbRecR1 = kMbR1Iters * kMbBlThreads;
+static_assert(kMbTilePx % kMbBlThreads == 0 && kMbTilePx <= 2048 && kBlendSlots <= 8,
+              "pixel record: whole iterations, 11-bit pixel, 4-bit slot");
+static_assert(kMbNRX <= 32 && kMbNRX * kMbNRY < kMbR1Inert, "records: 5-bit column, 10-bit entry");
+static_assert(kMbN2X <= 16 && kMbN2Y <= 32, "R1 record: 4-bit level-2 column, 5-bit row");
+constexpr int mb_rec_slots(int slots) { return slots <= 2 ? 2 : (slots <= 4 ? 4 : 8); }
+constexpr int mb_r1rec_words(int slots) { return 2 + mb_rec_slots(slots) / 2; }
+constexpr int mb_rec_words(int slots)
+{
+    return 2 * kMbTilePx + kMbRecR1 * mb_r1rec_words(slots);
+}
 struct KBlendPrepArgs {
     KParams P;
     uint8_t *owner;
@@ -250,6 +279,7 @@ struct KMbArgs {
     int f0, nf;                    // captures [f0, f0 + nf) of this launch
     int list0;                     // blend: first list entry of this launch
     int n_list;                    // blend: list entries in this launch (xcd_unit's nx)
+    uint32_t *rec;                 // [tiles][mb_rec_words(slots)] blend work records (prep)
 };
 
 // Band pass of the multi-band levels (mcs_mb_bands_c*): one wave per (band, kMbBandFrames

@@ -85,6 +85,7 @@ void mb_args(const mcs_plan *p, const mcs::KParams &P, mcs::KMbArgs &a)
     a.nf = 0;
     a.list0 = 0;
     a.n_list = p->t.n_blend;
+    a.rec = p->t.d_mbrec;
 }
 
 void band_args(const mcs_plan *p, const mcs::KParams &P, mcs::KMbBandArgs &a)

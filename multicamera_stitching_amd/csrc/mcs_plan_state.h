@@ -48,6 +48,7 @@ struct mcs_plan {
         uint64_t *d_mbdesc = nullptr;
         int32_t *d_mbtab = nullptr;
         int32_t *d_mbfoot = nullptr;
+        uint32_t *d_mbrec = nullptr;   // blend work records (mcs_kparams.h, mb_rec_words)
         uint16_t *d_mbg1 = nullptr;
         int32_t *d_mbg2 = nullptr;
         int mb_chunk = 0;

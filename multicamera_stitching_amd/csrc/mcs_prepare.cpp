@@ -458,6 +458,7 @@ static int prepare_multiband(const Api *A, mcs_plan *p, const Kernels *k, hipStr
     HIP_TRY(p->t.alloc(A, &p->t.d_mbdesc, (size_t)(n * S * samples)));
     HIP_TRY(p->t.alloc(A, &p->t.d_mbtab, (size_t)n * mcs::mb_tab_words(S)));
     HIP_TRY(p->t.alloc(A, &p->t.d_mbfoot, (size_t)n * S * 8));
+    HIP_TRY(p->t.alloc(A, &p->t.d_mbrec, (size_t)n * mcs::mb_rec_words(S)));
     // (level 1: 8 bytes an entry, level 2: C int32 an entry)
     HIP_TRY(p->t.alloc(A, &p->t.d_mbg1, (size_t)n * S * chunk * mcs::kMbNRX * mcs::kMbNRY * 4));
     HIP_TRY(p->t.alloc(A, &p->t.d_mbg2, (size_t)n * S * chunk * mcs::kMbN2X * mcs::kMbN2Y * C));
