@@ -169,6 +169,15 @@ int mcs_plan_set_lens(mcs_plan *plan, int cam, const double *K, const double *di
  * stops growing, one step back; +inf when there is none. */
 int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const double *uv, int n,
                       double *xy, double *r2max);
+/* The inverse of mcs_lens_map_host on the host: n raw-frame positions xy -> uv, the positions in
+ * the undistorted image (six Newton steps on the lens map from the raw position itself, in one
+ * fixed FP64 order: the arithmetic a lensed rig job runs on the device, bit for bit).  NaN, NaN
+ * where there is no valid inverse: the result is not finite, lies beyond the valid radius, or the
+ * lens map does not take it back to within 2^-20 px of the input on both axes (a raw position
+ * with no preimage inside the valid radius).  K / dist / n_dist and their status codes as
+ * mcs_lens_map_host. */
+int mcs_lens_unmap_host(const double *K, const double *dist, int n_dist, const double *xy, int n,
+                        double *uv);
 int mcs_plan_destroy(mcs_plan *plan);
 int mcs_plan_out_shape(const mcs_plan *plan, int *w, int *h, int *channels);
 int mcs_plan_describe(const mcs_plan *plan, mcs_flat_desc *out);
@@ -567,6 +576,21 @@ int mcs_rig_job_set_exposure(mcs_rig_job *job, int step_log2, double alpha, doub
  * 1.0 and 256.  Any pointer may be NULL.  No temporal smoothing is done: a caller that wants it
  * has the values here. */
 int mcs_rig_job_gains(const mcs_rig_job *job, double *gains, uint16_t *q, int *enabled);
+/* Lens of camera `cam` (0 .. n_cams - 1; in a batch job camera c of every capture takes lens
+ * c mod n_cams): the job is fed RAW frames.  ORB detects and describes on them; the positions of
+ * the matches that pass the ratio test go through the inverse lens of their own camera
+ * (mcs_lens_unmap_host's arithmetic, on the device inside the capture's launch chain, on the host
+ * on the per-call path) and are rounded to float; a match either of whose positions has no valid
+ * inverse is dropped (n_matches counts the survivors, in query order); RANSAC and the refinement
+ * then estimate the pair homographies between the UNDISTORTED images, and
+ * mcs_rig_job_wait_stitch[_batch] sets the same lenses on the capture's plan
+ * (mcs_plan_set_lens), so paste, feather and the exposure sweep render the raw frames.  A camera
+ * with a lens beside one without is legal; a job with no lens runs exactly what it ran before
+ * this entry point.  K == NULL removes the lens.  K, dist, n_dist and the status codes as
+ * mcs_plan_set_lens; MCS_E_INVALID while a capture is in flight.  Drops the job's captured
+ * graph (the next capture records the chain again); touches no device itself. */
+int mcs_rig_job_set_lens(mcs_rig_job *job, int cam, const double *K, const double *dist,
+                         int n_dist);
 /* Captures the job finished on the device path (one launch chain) and on the per-call path (a
  * device ranking overflow, or MCS_RIG_PATH=calls). */
 int mcs_rig_job_counts(const mcs_rig_job *job, int *device_captures, int *call_captures);

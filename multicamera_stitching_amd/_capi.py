@@ -56,6 +56,7 @@ EXPORTS = (
     "mcs_gain_apply_device", "mcs_stitch_device_gained", "mcs_stitch_direct_gained",
     "mcs_rig_job_set_blend", "mcs_plan_overlap_stats_direct",
     "mcs_plan_overlap_stats_direct_async", "mcs_rig_job_set_exposure", "mcs_rig_job_gains",
+    "mcs_lens_unmap_host", "mcs_rig_job_set_lens",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -293,6 +294,10 @@ def load() -> ctypes.CDLL:
         L.mcs_plan_set_lens.restype = I
         L.mcs_lens_map_host.argtypes = [P, P, I, P, I, P, P]
         L.mcs_lens_map_host.restype = I
+        L.mcs_lens_unmap_host.argtypes = [P, P, I, P, I, P]
+        L.mcs_lens_unmap_host.restype = I
+        L.mcs_rig_job_set_lens.argtypes = [P, I, P, P, I]
+        L.mcs_rig_job_set_lens.restype = I
         L.mcs_match_l2_knn2.argtypes = [P, I, P, I, I, P, P, P, I, P]
         L.mcs_match_l2_knn2.restype = I
         L.mcs_match_l2_knn2_host.argtypes = [P, I, P, I, I, P, P, P, I]
@@ -1127,6 +1132,19 @@ class RigJob:
         check(self._lib.mcs_rig_job_set_exposure(self._h, int(step_log2), float(alpha),
                                                  float(beta)))
 
+    def set_lens(self, cam: int, K, dist=None):
+        """mcs_rig_job_set_lens: camera `cam` delivers RAW frames; its matched keypoints go
+        through the inverse lens before the pair homographies are estimated, and wait_stitch
+        sets the lens on the capture's plan.  K=None removes the lens.  Between captures only."""
+        if K is None:
+            check(self._lib.mcs_rig_job_set_lens(self._h, int(cam), None, None, 0))
+            return self
+        k, d = _lens_args(K, dist)
+        check(self._lib.mcs_rig_job_set_lens(self._h, int(cam), k.ctypes.data_as(ctypes.c_void_p),
+                                             d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
+                                             int(d.size)))
+        return self
+
     def gains(self):
         """(gains, q, enabled) of the last wait_stitch (mcs_rig_job_gains): float64 and uint16
         arrays of shape (n_cams,), or (captures, n_cams) for a batch job; 1.0 and 256 before the
@@ -1238,6 +1256,22 @@ def lens_map_host(K, dist, uv, with_r2max: bool = False):
                               pts.ctypes.data_as(ctypes.c_void_p), int(pts.size // 2),
                               out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(r2)))
     return (out, r2.value) if with_r2max else out
+
+
+def lens_unmap_host(K, dist, xy):
+    """mcs_lens_unmap_host: raw-frame positions xy (..., 2) -> positions in the undistorted image
+    (same shape, float64; NaN, NaN where the lens has no valid inverse)."""
+    L = load()
+    k, d = _lens_args(K, dist)
+    pts = np.ascontiguousarray(np.asarray(xy, np.float64))
+    if pts.shape[-1:] != (2,):
+        raise ValueError("xy must have shape (..., 2)")
+    out = np.empty_like(pts)
+    check(L.mcs_lens_unmap_host(k.ctypes.data_as(ctypes.c_void_p),
+                                d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
+                                int(d.size), pts.ctypes.data_as(ctypes.c_void_p),
+                                int(pts.size // 2), out.ctypes.data_as(ctypes.c_void_p)))
+    return out
 
 
 def match_l2_knn2(query, train, device: int = 0):

@@ -681,6 +681,24 @@ int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const dou
     return MCS_OK;
 }
 
+int mcs_lens_unmap_host(const double *K, const double *dist, int n_dist, const double *xy, int n,
+                        double *uv)
+{
+    mcs::clear_error();
+    if (!K || (n_dist > 0 && !dist) || n < 0 || (n > 0 && (!xy || !uv)))
+        return mcs::fail(MCS_E_INVALID, "NULL K/dist/xy/uv");
+    mcs::Lens L;
+    const int rc = mcs::lens_from(K, dist, n_dist < 0 ? 0 : n_dist, &L);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++) {
+        double u = std::nan(""), v = std::nan("");
+        (void)mcs::lens_invert(L, xy[2 * i], xy[2 * i + 1], u, v);
+        uv[2 * i] = u;
+        uv[2 * i + 1] = v;
+    }
+    return MCS_OK;
+}
+
 int mcs_plan_find_seams(mcs_plan *p, const uint8_t *const *cams, int method, int scale_log2)
 {
     mcs::clear_error();

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "mcs_fparams.h"
+#include "mcs_lens_core.h"
 #include "mcs_ransac_core.h"
 #include "mcs_orb_core.h"
 
@@ -882,10 +883,52 @@ extern "C" __global__ __launch_bounds__(64) void mcs_rig_knn2(const mcs::KRigArg
                a.keys + (int64_t)2 * p * a.kstride, nq, nt, a.per_chunk, blockIdx.x, blockIdx.y);
 }
 
+// Lensed jobs only (a.lens != nullptr), before mcs_rig_match: grid (ceil(kstride / 256), pairs),
+// block 256, one thread per query q of pair p.  A query that passes the ratio test gets its own
+// and its best train keypoint's position carried through the inverse lens of their cameras
+// (lens_invert, each result rounded to float; a camera without a lens keeps its position) into
+// lpts[4 q ..]; lpts[4 q] = NaN when either position has no valid inverse.  Its own small kernel:
+// the FP64 Newton steps stay out of mcs_rig_match's 1024-thread block (128 VGPRs per lane there).
+extern "C" __global__ __launch_bounds__(256) void mcs_rig_unlens(const mcs::KRigArgs a)
+{
+    using namespace mcs;
+    const int p = blockIdx.y, q = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    const int nq = a.sel[2 * (p + 1) + 1] ? 0 : a.sel[2 * (p + 1)];
+    const int nt = a.sel[2 * p + 1] ? 0 : a.sel[2 * p];
+    if (nt <= 0 || q >= nq) return;
+    const uint32_t *keys = a.keys + (int64_t)2 * p * a.kstride;
+    const uint32_t k0 = keys[2 * q], k1 = keys[2 * q + 1];
+    if (!(k1 != kKeyNone && (double)(k0 >> kKnnKeyShift) < (double)(k1 >> kKnnKeyShift) * a.ratio))
+        return;
+    const int *kq = a.kp + (int64_t)3 * (p + 1) * a.kstride, *kt = a.kp + (int64_t)3 * p * a.kstride;
+    const int t = (int)(k0 & (kKnnMaxTrain - 1));
+    const int cq = (p + 1) % a.n_cams, ct = p % a.n_cams;
+    const Lens *lens = reinterpret_cast<const Lens *>(a.lens);
+    double x = (double)((float)kq[3 * q + 1] * a.lscale[kq[3 * q]]);
+    double y = (double)((float)kq[3 * q + 2] * a.lscale[kq[3 * q]]);
+    double u = (double)((float)kt[3 * t + 1] * a.lscale[kt[3 * t]]);
+    double v = (double)((float)kt[3 * t + 2] * a.lscale[kt[3 * t]]);
+    bool ok = true;
+    if ((a.lens_mask >> cq) & 1u) {
+        ok = lens_invert(lens[cq], x, y, x, y);
+        x = (double)(float)x, y = (double)(float)y;
+    }
+    if (ok && ((a.lens_mask >> ct) & 1u)) {
+        ok = lens_invert(lens[ct], u, v, u, v);
+        u = (double)(float)u, v = (double)(float)v;
+    }
+    double *o = a.lpts + 4 * ((int64_t)p * a.kstride + q);
+    o[0] = ok ? x : __builtin_nan("");
+    o[1] = y;
+    o[2] = u;
+    o[3] = v;
+}
+
 // grid (pairs), block 1024: pair p's kNN-2 keys -> Lowe's ratio (a second neighbour exists and
 // (double)d0 < (double)d1 * ratio, strict) -> the passing queries' positions (query and its best
 // train keypoint, level-0 pixels as the float (float)x * lscale[level]) compacted in query order
-// into pts; info[4 p] = their count.
+// into pts; info[4 p] = their count.  Lensed jobs (a.lens): the positions are mcs_rig_unlens's,
+// and a query passes only if both of its positions have a valid inverse.
 extern "C" __global__ __launch_bounds__(1024) void mcs_rig_match(const mcs::KRigArgs a)
 {
     using namespace mcs;
@@ -895,6 +938,7 @@ extern "C" __global__ __launch_bounds__(1024) void mcs_rig_match(const mcs::KRig
     const uint32_t *keys = a.keys + (int64_t)2 * p * a.kstride;
     const int *kq = a.kp + (int64_t)3 * (p + 1) * a.kstride, *kt = a.kp + (int64_t)3 * p * a.kstride;
     double *pts = a.pts + (int64_t)4 * p * a.kstride;
+    const double *lp = a.lens ? a.lpts + (int64_t)4 * p * a.kstride : nullptr;
     __shared__ int wcount[16];
     int base = 0;
     for (int q0 = 0; q0 < (nt > 0 ? nq : 0); q0 += 1024) {
@@ -906,6 +950,7 @@ extern "C" __global__ __launch_bounds__(1024) void mcs_rig_match(const mcs::KRig
             const uint32_t k1 = keys[2 * q + 1];
             pass = k1 != kKeyNone &&
                    (double)(k0 >> kKnnKeyShift) < (double)(k1 >> kKnnKeyShift) * a.ratio;
+            if (pass && lp) pass = lp[4 * q] == lp[4 * q];   // (NaN: no valid inverse)
         }
         const unsigned long long bal = __ballot(pass);
         if (lane == 0) wcount[wave] = __popcll(bal);
@@ -918,10 +963,14 @@ extern "C" __global__ __launch_bounds__(1024) void mcs_rig_match(const mcs::KRig
         if (pass) {
             const int o = base + before + __popcll(bal & ((1ull << lane) - 1ull));
             const int t = (int)(k0 & (kKnnMaxTrain - 1));
-            pts[4 * o] = (double)((float)kq[3 * q + 1] * a.lscale[kq[3 * q]]);
-            pts[4 * o + 1] = (double)((float)kq[3 * q + 2] * a.lscale[kq[3 * q]]);
-            pts[4 * o + 2] = (double)((float)kt[3 * t + 1] * a.lscale[kt[3 * t]]);
-            pts[4 * o + 3] = (double)((float)kt[3 * t + 2] * a.lscale[kt[3 * t]]);
+            if (lp) {
+                for (int i = 0; i < 4; i++) pts[4 * o + i] = lp[4 * q + i];
+            } else {
+                pts[4 * o] = (double)((float)kq[3 * q + 1] * a.lscale[kq[3 * q]]);
+                pts[4 * o + 1] = (double)((float)kq[3 * q + 2] * a.lscale[kq[3 * q]]);
+                pts[4 * o + 2] = (double)((float)kt[3 * t + 1] * a.lscale[kt[3 * t]]);
+                pts[4 * o + 3] = (double)((float)kt[3 * t + 2] * a.lscale[kt[3 * t]]);
+            }
         }
         base += total;
         __syncthreads();

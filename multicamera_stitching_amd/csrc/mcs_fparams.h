@@ -176,6 +176,16 @@ struct KRigArgs {
     double ratio, t2;
     int kstride, iters, per_chunk;
     uint32_t seed;
+    // Lensed jobs (mcs_rig_job_set_lens; lens == nullptr: none, and nothing below is read): the
+    // job's lens table, camera c's row (mcs_lens_core.h Lens) at lens + kLensDoubles (c % n_cams)
+    // when bit c % n_cams of lens_mask is set; lpts: pair p's at lpts + 4 p kstride, per QUERY q
+    // the positions of q and its best train keypoint through their inverse lenses
+    // (mcs_rig_unlens writes them for the queries that pass the ratio test, [4 q] NaN when either
+    // has no valid inverse; mcs_rig_match compacts them)
+    const double *lens;
+    double *lpts;
+    uint32_t lens_mask;
+    int n_cams;
 };
 
 // Graph-cut seams on the device (mcs_seam.cpp; spec oracle/orc_seam.c): the

@@ -61,6 +61,59 @@ MCS_LENS_HD bool lens_apply(const Lens &L, double u, double v, double &xr, doubl
     return true;
 }
 
+// The lens polynomial alone, lens_apply's arithmetic without the valid-radius rule (the iterates
+// of lens_invert may leave the radius on their way).
+MCS_LENS_HD void lens_poly(const Lens &L, double u, double v, double &xr, double &yr)
+{
+    const double x = (u - L.cx) / L.fx, y = (v - L.cy) / L.fy;
+    const double x2 = x * x, y2 = y * y;
+    const double r2 = x2 + y2, _2xy = 2 * x * y;
+    const double kr = lens_num(L, r2) / lens_den(L, r2);
+    const double xd = x * kr + L.k[2] * _2xy + L.k[3] * (r2 + 2 * x2) + L.k[8] * r2 +
+                      L.k[9] * r2 * r2;
+    const double yd = y * kr + L.k[2] * (r2 + 2 * y2) + L.k[3] * _2xy + L.k[10] * r2 +
+                      L.k[11] * r2 * r2;
+    xr = L.fx * xd + L.cx;
+    yr = L.fy * yd + L.cy;
+}
+
+// The inverse: (xr, yr) of the raw frame -> (u, v) of the undistorted image (mcs_rig_job_set_lens:
+// matched keypoints of raw frames carried into the image their homography is estimated in).
+// kLensInvIters Newton steps on lens_poly from the raw position itself, the Jacobian by forward
+// differences of 1 / 1024 px (a power of two: the quotient is a product), the 2 x 2 solve by
+// Cramer's rule; a fixed count, so host and device run the same operations.  Valid iff the result
+// is finite, inside the valid radius, and lens_apply takes it back to within kLensInvTol px of
+// (xr, yr) on both axes -- which rejects raw positions without a preimage inside the radius, where
+// the iteration ends somewhere arbitrary.  false: u, v untouched.
+constexpr int kLensInvIters = 6;
+constexpr double kLensInvTol = 1.0 / 1048576.0;   // 2^-20 px (half a float ulp at x >= 1024: 2^-14)
+MCS_LENS_HD bool lens_invert(const Lens &L, double xr, double yr, double &u, double &v)
+{
+    const double h = 1.0 / 1024.0, ih = 1024.0;
+    double pu = xr, pv = yr;
+    for (int it = 0; it < kLensInvIters; it++) {
+        double fx0, fy0, fx1, fy1, fx2, fy2;
+        lens_poly(L, pu, pv, fx0, fy0);
+        lens_poly(L, pu + h, pv, fx1, fy1);
+        lens_poly(L, pu, pv + h, fx2, fy2);
+        const double a = (fx1 - fx0) * ih, b = (fx2 - fx0) * ih;
+        const double c = (fy1 - fy0) * ih, d = (fy2 - fy0) * ih;
+        const double ex = fx0 - xr, ey = fy0 - yr;
+        const double det = a * d - b * c;
+        pu = pu - (d * ex - b * ey) / det;
+        pv = pv - (a * ey - c * ex) / det;
+    }
+    if (!(pu - pu == 0.0 && pv - pv == 0.0)) return false;   // inf or NaN
+    double bx, by;
+    if (!lens_apply(L, pu, pv, bx, by)) return false;
+    const double dx = bx - xr, dy = by - yr;
+    if (!(dx <= kLensInvTol && dx >= -kLensInvTol && dy <= kLensInvTol && dy >= -kLensInvTol))
+        return false;
+    u = pu;
+    v = pv;
+    return true;
+}
+
 #if !defined(__HIP_DEVICE_COMPILE__)
 // The valid radius squared of L's radial polynomial (L.r2max is not read).
 static inline double lens_r2max(const Lens &L)

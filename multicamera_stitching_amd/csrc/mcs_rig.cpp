@@ -22,6 +22,11 @@
 // ORBs side by side, a pair queued as soon as both of its cameras' ORBs are done, the last pair
 // marks the job done.
 //
+// Lenses (mcs_rig_job_set_lens): the job is fed raw frames.  ORB runs on them as they are; the
+// positions of the ratio-passing matches go through the inverse lens of their cameras
+// (mcs_lens_core.h lens_invert: mcs_rig_unlens in the chain, unlens() on the per-call path), a
+// match without a valid inverse is dropped, and the capture's plan gets the same lenses.
+//
 // Either way a job runs on libmcs's worker threads and mcs_rig_job_submit returns at once, so a
 // caller that keeps several jobs in flight overlaps one capture's estimation with another's.
 #include <algorithm>
@@ -29,6 +34,7 @@
 #include <cmath>
 #include <condition_variable>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <memory>
@@ -107,6 +113,7 @@ struct RigDevice {
     unsigned pyr_blocks = 0, knn_qblocks = 0, knn_chunks = 0;
     size_t o_cnt = 0, cnt_bytes = 0, o_keys = 0, keys_bytes = 0, o_blob = 0;
     size_t o_sel = 0, o_info = 0, o_hbest = 0, o_mask = 0, o_pts = 0;   // within the blob
+    size_t o_lens = 0, o_lpts = 0;   // the lens table (n_cams rows) and mcs_rig_unlens's positions
     mcs::KGrayArgs ga;
     mcs::KOrbBuildArgs ba;
     mcs::KOrbPyrArgs pa;
@@ -157,9 +164,37 @@ struct mcs_rig_job {
     std::vector<double> gains;
     std::vector<uint16_t> gain_q;
     int64_t *d_stats = nullptr, *h_stats = nullptr;
+    // per-camera lenses (mcs_rig_job_set_lens): bit c of lens_mask: camera c has one; lens[c] is
+    // its row of the device table (uploaded into the job's buffer before the next capture's chain
+    // when lens_stale), lens_K / lens_dist / lens_nd what the capture's plan is given
+    uint32_t lens_mask = 0;
+    bool lens_stale = false;
+    mcs::Lens lens[MCS_MAX_CAMS];
+    double lens_K[MCS_MAX_CAMS][9], lens_dist[MCS_MAX_CAMS][14];
+    int lens_nd[MCS_MAX_CAMS];
 };
 
 namespace {
+
+// MCS_RIG_PATH=calls: every capture takes the per-call path (read per capture).
+bool calls_forced()
+{
+    const char *e = getenv("MCS_RIG_PATH");
+    return e && !strcmp(e, "calls");
+}
+
+// A matched position of camera c (a float) through the camera's inverse lens, rounded to float
+// again -- what mcs_rig_unlens does on the device; false: no valid inverse, the match is dropped.
+bool unlens(const mcs_rig_job *j, int c, float &x, float &y)
+{
+    c %= j->n_cams;
+    if (!((j->lens_mask >> c) & 1u)) return true;
+    double u, v;
+    if (!mcs::lens_invert(j->lens[c], (double)x, (double)y, u, v)) return false;
+    x = (float)u;
+    y = (float)v;
+    return true;
+}
 
 void finish(mcs_rig_job *j)
 {
@@ -189,10 +224,12 @@ void pair_task(mcs_rig_job *j, int k)
                 if (idx[2 * q + 1] < 0) continue;
                 if (!((double)dist[2 * q] < (double)dist[2 * q + 1] * (double)j->ratio)) continue;
                 const int t = idx[2 * q];
-                src.push_back(fa.xy[2 * q]);
-                src.push_back(fa.xy[2 * q + 1]);
-                dst.push_back(fb.xy[2 * t]);
-                dst.push_back(fb.xy[2 * t + 1]);
+                float x = fa.xy[2 * q], y = fa.xy[2 * q + 1], u = fb.xy[2 * t], v = fb.xy[2 * t + 1];
+                if (j->lens_mask && !(unlens(j, k + 1, x, y) && unlens(j, k, u, v))) continue;
+                src.push_back(x);
+                src.push_back(y);
+                dst.push_back(u);
+                dst.push_back(v);
             }
             j->n_matches[k] = (int)src.size() / 2;
         }
@@ -280,6 +317,8 @@ int device_setup(mcs_rig_job *j)
     d.o_keys = take(d.keys_bytes);
     const size_t o_hyps = take((size_t)P * j->iters * 8 * sizeof(double));
     const size_t o_scores = take((size_t)P * j->iters * sizeof(int32_t));
+    d.o_lens = take(sizeof(j->lens));
+    d.o_lpts = take((size_t)P * K * 4 * sizeof(double));
     // the copy-back blob, contiguous
     d.o_blob = o;
     size_t b = 0;
@@ -376,6 +415,9 @@ int device_setup(mcs_rig_job *j)
     d.ra.kstride = K;
     d.ra.iters = j->iters;
     d.ra.seed = j->seed;
+    d.ra.lpts = reinterpret_cast<double *>(B + d.o_lpts);
+    d.ra.n_cams = j->n_cams;
+    j->lens_stale = true;   // (a fresh buffer: the table, if any, is uploaded before the chain)
     // kNN-2 blocks: query waves x train chunks x pairs, enough to fill the chip (as the per-call
     // matcher sizes them; the result does not depend on the chunking)
     d.knn_qblocks = (unsigned)((K + mcs::kKnnQueriesPerBlock - 1) / mcs::kKnnQueriesPerBlock);
@@ -473,6 +515,9 @@ int enqueue_chain(mcs_rig_job *j, const mcs::rt::Api *A, const mcs::feat::Featur
     if (rc == MCS_OK)
         rc = launch(A, k->rig_knn2, d.knn_qblocks, d.knn_chunks, mcs::kKnnLanes, &d.ra,
                     sizeof(d.ra), s, (unsigned)P);
+    if (rc == MCS_OK && d.ra.lens)
+        rc = launch(A, k->rig_unlens, (unsigned)((d.K + 255) / 256), (unsigned)P, 256, &d.ra,
+                    sizeof(d.ra), s);
     if (rc == MCS_OK) rc = launch(A, k->rig_match, (unsigned)P, 1, 1024, &d.ra, sizeof(d.ra), s);
     if (rc == MCS_OK)
         rc = launch(A, k->rig_hyp, (unsigned)((j->iters + 63) / 64), (unsigned)P, 64, &d.ra,
@@ -508,6 +553,19 @@ int device_capture(mcs_rig_job *j, bool *overflow)
     hipStream_t s = d.s;
     if (j->wait_event) HIP_TRY(A->hipStreamWaitEvent(s, (hipEvent_t)j->wait_event, 0));
     hipError_t e = hipSuccess;
+    if (j->lens_stale) {
+        // the lenses changed: the table into the job's buffer (stream-ordered before the chain;
+        // the job is not submitted again before this capture ends, so the host rows stay), the
+        // kernels' arguments, and the graph that recorded the old ones dropped
+        if (j->lens_mask)
+            HIP_TRY(A->hipMemcpyAsync(d.buf + d.o_lens, j->lens, sizeof(j->lens),
+                                      hipMemcpyHostToDevice, s));
+        d.ra.lens = j->lens_mask ? reinterpret_cast<const double *>(d.buf + d.o_lens) : nullptr;
+        d.ra.lens_mask = j->lens_mask;
+        if (d.exec) (void)A->hipGraphExecDestroy(d.exec);
+        d.exec = nullptr;
+        j->lens_stale = false;
+    }
     if ((rc = enqueue_resets(j, A, s)) != MCS_OK) return rc;
     if (d.pyr_blocks > 0) {
         if (!d.exec || d.graph_frames != j->frames) {
@@ -587,8 +645,8 @@ void start_calls(mcs_rig_job *j)
 
 void capture_task(mcs_rig_job *j)
 {
-    bool overflow = false;
-    const int rc = device_capture(j, &overflow);
+    bool overflow = calls_forced();
+    const int rc = overflow ? MCS_OK : device_capture(j, &overflow);
     if (rc == MCS_OK && !overflow) {
         j->captures_device++;
         finish(j);
@@ -747,7 +805,10 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         r = mcs_plan_create(st, np, j->w, j->h, j->channels, interp, j->device, &plan);
         if (r) return r;
         int w = 0, h = 0, c = 0;
-        if (j->blend != MCS_BLEND_NONE) r = mcs_plan_set_blend(plan, j->blend);
+        for (int cam = 0; cam < N && r == MCS_OK; cam++)
+            if ((j->lens_mask >> cam) & 1u)
+                r = mcs_plan_set_lens(plan, cam, j->lens_K[cam], j->lens_dist[cam], j->lens_nd[cam]);
+        if (r == MCS_OK && j->blend != MCS_BLEND_NONE) r = mcs_plan_set_blend(plan, j->blend);
         if (r == MCS_OK) r = mcs_plan_out_shape(plan, &w, &h, &c);
         if (r == MCS_OK && ((int64_t)w * c > out_pitch || (int64_t)h * out_pitch > out_capacity))
             r = mcs::fail(MCS_E_SHAPE, "mosaic %d x %d does not fit the output (pitch %lld, "
@@ -852,6 +913,35 @@ int mcs_rig_job_set_exposure(mcs_rig_job *j, int step_log2, double alpha, double
         j->gains.assign(j->ci, 1.0);
         j->gain_q.assign(j->ci, 256);
     }
+    return MCS_OK;
+}
+
+int mcs_rig_job_set_lens(mcs_rig_job *j, int cam, const double *K, const double *dist, int n_dist)
+{
+    mcs::clear_error();
+    if (!j) return mcs::fail(MCS_E_INVALID, "NULL job");
+    if (cam < 0 || cam >= j->n_cams)
+        return mcs::fail(MCS_E_INVALID, "camera %d (0..%d)", cam, j->n_cams - 1);
+    mcs::Lens L;
+    if (K) {
+        if (n_dist < 0 || (n_dist > 0 && !dist)) return mcs::fail(MCS_E_INVALID, "NULL dist");
+        const int rc = mcs::lens_from(K, dist, n_dist, &L);
+        if (rc) return rc;
+    }
+    std::lock_guard<std::mutex> lk(j->mu);
+    if (j->busy && !j->done) return mcs::fail(MCS_E_INVALID, "job still running");
+    if (K) {
+        j->lens[cam] = L;
+        std::memcpy(j->lens_K[cam], K, sizeof(j->lens_K[cam]));
+        for (int i = 0; i < 14; i++) j->lens_dist[cam][i] = i < n_dist ? dist[i] : 0.0;
+        j->lens_nd[cam] = n_dist;
+        j->lens_mask |= 1u << cam;
+    } else {
+        if (!((j->lens_mask >> cam) & 1u)) return MCS_OK;   // none to remove
+        j->lens[cam] = mcs::Lens();
+        j->lens_mask &= ~(1u << cam);
+    }
+    j->lens_stale = true;
     return MCS_OK;
 }
 

@@ -156,7 +156,7 @@ class CaptureEstimator:
                  iters: int = 2000, seed: int = 0, super_mode: bool = False,
                  interp: int = _capi.MCS_INTER_LINEAR, device: int = 0, threads: int = None,
                  captures_per_job: int = 1, blend: int = _capi.MCS_BLEND_NONE,
-                 exposure: int = None):
+                 exposure: int = None, lenses=None):
         self.n_cams, self.w, self.h, self.c = n_cams, width, height, channels
         # per-capture exposure gains of collect_stitch (mcs_rig_job_set_exposure): the grid step
         # step_log2 (0..4) of the overlap statistics, or None for none; .gains: the last
@@ -185,6 +185,8 @@ class CaptureEstimator:
         self.last_H = [None] * (n_cams - 1)
         self.stats = {}
         self._jobs = []
+        self.lenses = {}
+        self.set_lenses(lenses)
 
     def close(self):
         for j in self._jobs:
@@ -194,6 +196,27 @@ class CaptureEstimator:
         self.ahead.shutdown()
         self.fpool.shutdown()
         self.pool.shutdown()
+
+    def set_lenses(self, lenses):
+        """Per-camera lenses {camera index: (K, dist)}: the estimator is fed RAW frames
+        (mcs_rig_job_set_lens).  Every slot's rig job, the Python-issued steps (pair_homography /
+        estimate_from carry the matched keypoints through lens_unmap_host and drop the ones
+        without a valid inverse) and the plans of plan() / stitch() take them; the pair
+        homographies relate the cameras' UNDISTORTED images.  None or {} removes all; a camera
+        that is missing (or maps to None) has no lens.  Between captures only."""
+        table = {}
+        for cam, lens in dict(lenses or {}).items():
+            if not 0 <= int(cam) < self.n_cams:
+                raise KeyError(f"camera {cam} (0..{self.n_cams - 1})")
+            if lens is None:
+                continue
+            K, dist = lens
+            table[int(cam)] = _capi._lens_args(K, dist)
+        for job in self._jobs:
+            if job is not None:
+                for cam in range(self.n_cams):
+                    job.set_lens(cam, *table.get(cam, (None, None)))
+        self.lenses = table
 
     def _job(self, slot):
         if slot >= len(self._jobs):
@@ -207,6 +230,8 @@ class CaptureEstimator:
                 self._jobs[slot].set_blend(self.blend)
             if self.exposure is not None:
                 self._jobs[slot].set_exposure(self.exposure)
+            for cam, (K, dist) in sorted(self.lenses.items()):
+                self._jobs[slot].set_lens(cam, K, dist)
         return self._jobs[slot]
 
     def submit(self, frame_ptrs, wait_event: int = 0, slot: int = 0):
@@ -286,15 +311,29 @@ class CaptureEstimator:
             return self.features(frame_ptrs, self.fpool)
         return self.ahead.submit(run)
 
-    def pair_homography(self, fa, fb):
+    def _unlens(self, cam, xy):
+        """float32 raw positions of camera `cam` -> float32 undistorted ones (NaN: no valid
+        inverse), as the rig job carries them; a camera without a lens keeps its positions."""
+        if cam not in self.lenses:
+            return xy
+        K, dist = self.lenses[cam]
+        return _capi.lens_unmap_host(K, dist, xy.astype(np.float64)).astype(np.float32)
+
+    def pair_homography(self, fa, fb, cam_a: int = None, cam_b: int = None):
         """Camera A -> camera B (A = query, as matchKeypoints' ptsA): H or None, matches,
-        inliers."""
+        inliers.  cam_a / cam_b: the cameras' indices, for their lenses (set_lenses); a match
+        either of whose positions has no valid inverse is dropped."""
         idx, dist = _capi.match_hamming_knn2(fa["desc"], fb["desc"], self.device)
         q = ratio_filter(idx, dist, self.ratio)
+        src = np.ascontiguousarray(fa["xy"][q], np.float32).reshape(-1, 2)
+        dst = np.ascontiguousarray(fb["xy"][idx[q, 0]], np.float32).reshape(-1, 2)
+        if self.lenses and len(q):
+            src, dst = self._unlens(cam_a, src), self._unlens(cam_b, dst)
+            keep = ~(np.isnan(src).any(axis=1) | np.isnan(dst).any(axis=1))
+            q = q[keep]
+            src, dst = np.ascontiguousarray(src[keep]), np.ascontiguousarray(dst[keep])
         if len(q) <= 4:                       # matchKeypoints needs more than 4 (:437)
             return None, len(q), 0
-        src = np.ascontiguousarray(fa["xy"][q], np.float32)
-        dst = np.ascontiguousarray(fb["xy"][idx[q, 0]], np.float32)
         H, mask = _capi.ransac_homography(src, dst, self.thresh, self.iters, self.seed,
                                           device=self.device)
         n_in = int(mask.sum()) if mask is not None else 0
@@ -309,7 +348,7 @@ class CaptureEstimator:
     def estimate_from(self, feats):
         """The pair step issued from Python, from the capture's features (features /
         features_async); same result as the rig job."""
-        res = list(self.pool.map(lambda k: self.pair_homography(feats[k + 1], feats[k]),
+        res = list(self.pool.map(lambda k: self.pair_homography(feats[k + 1], feats[k], k + 1, k),
                                  range(self.n_cams - 1)))
         pair_H = []
         for k, (H, n_m, n_in) in enumerate(res):
@@ -325,8 +364,11 @@ class CaptureEstimator:
         from .StitcherClass import _stage_desc
         shapes = [(self.h, self.w, self.c)] * self.n_cams
         stages = chain_stages(pair_H, shapes, self.super_mode)
-        return _capi.Plan([_stage_desc(sb) for sb in stages], self.w, self.h, self.c, self.interp,
-                          device=self.device), stages
+        plan = _capi.Plan([_stage_desc(sb) for sb in stages], self.w, self.h, self.c, self.interp,
+                          device=self.device)
+        for cam, (K, dist) in sorted(self.lenses.items()):
+            plan.set_lens(cam, K, dist)
+        return plan, stages
 
     def stitch(self, frame_ptrs, pair_H, out_ptr: int, out_pitch: int, out_capacity: int,
                stream: int = 0):

@@ -16,6 +16,12 @@ four frames uploaded once (pageable host -> device, timed), ORB on the device co
 RANSAC, the chain geometry and a fresh plan on the host, and the capture stitched with its own
 homographies by mcs_stitch_direct; the line then reports captures/s and stitched MPix/s, and
 checks one capture's mosaic against the CPU restatement of the same geometry.
+
+--lens (with --stitch): every camera delivers RAW frames through a mild lens (tools/lens_bench.py's
+focal length and distortion): the frames are distorted once on the host before the run, the
+estimator is given the lenses (CaptureEstimator(lenses=...): matched keypoints through the inverse
+lens, a lensed per-capture plan), and the errors are still measured against the clean rig's truth.
+The CPU restatement cannot express a lens, so that check is left out (null).
 """
 import argparse
 import json
@@ -98,6 +104,38 @@ BLENDS = {"none": 0, "seam": 3, "feather": 1}
 BLEND_NAMES = {"none": "paste", "seam": "seam", "feather": "feather"}
 
 
+def bench_lens(w, h):
+    """(K, dist) of --lens: lens_bench.py's mild lens, centred."""
+    from lens_bench import DIST, FOCAL
+    return [[FOCAL, 0, (w - 1) / 2.0], [0, FOCAL, (h - 1) / 2.0], [0, 0, 1]], list(DIST)
+
+
+def raw_frames(frames, K, dist):
+    """The frames a camera with lens (K, dist) delivers of the undistorted views `frames`:
+    raw[p] = bilinear(clean, inverse lens of p), 0 where there is none; past the clean view's
+    edge (a barrel lens sees further) its nearest edge pixel."""
+    from multicamera_stitching_amd import _capi
+    h, w = frames[0].shape[:2]
+    y, x = np.mgrid[0:h, 0:w].astype(np.float64)
+    uv = _capi.lens_unmap_host(K, dist, np.stack([x, y], axis=-1))
+    ok = ~np.isnan(uv[..., 0])
+    u = np.where(ok, np.clip(uv[..., 0], 0, w - 1), -10.0)
+    v = np.where(ok, np.clip(uv[..., 1], 0, h - 1), -10.0)
+    x0, y0 = np.floor(u).astype(np.int64), np.floor(v).astype(np.int64)
+    ax, ay = (u - x0)[..., None], (v - y0)[..., None]
+    out = []
+    for f in frames:
+        acc = np.zeros(f.shape, np.float64)
+        for dx, dy, wt in ((0, 0, (1 - ax) * (1 - ay)), (1, 0, ax * (1 - ay)),
+                           (0, 1, (1 - ax) * ay), (1, 1, ax * ay)):
+            xx, yy = x0 + dx, y0 + dy
+            inside = (xx >= 0) & (xx < w) & (yy >= 0) & (yy < h)
+            val = f[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)].astype(np.float64)
+            acc += np.where(inside[..., None], val, 0.0) * wt
+        out.append(np.clip(np.rint(acc), 0, 255).astype(np.uint8))
+    return out
+
+
 def cpu_render(oracle, plan, frames, blend, q=None):
     """The CPU restatement of the mosaic the capture's stitch rendered; q: the capture's
     quantised exposure gains (--exposure), applied to the frames first."""
@@ -151,6 +189,9 @@ def main():
     ap.add_argument("--camera-scales", default=None, metavar="S0,S1,..",
                     help="scale camera i's frame bytes by Si (clipped to 255): cameras on different "
                          "exposures, so that --exposure finds gains other than 1")
+    ap.add_argument("--lens", action="store_true",
+                    help="with --stitch: raw frames through lens_bench.py's mild lens on every "
+                         "camera, the estimator given the lenses")
     ap.add_argument("--pinned", action="store_true",
                     help="camera frames in pinned host buffers (default: pageable numpy arrays, "
                          "as the reference's capture loop holds them)")
@@ -159,10 +200,17 @@ def main():
                                           not args.python_stitch):
         raise SystemExit("--exposure needs --stitch --pipelined --overlap and the in-library "
                          "stitch")
+    if args.lens and not args.stitch:
+        raise SystemExit("--lens needs --stitch")
     from multicamera_stitching_amd import rig
     W, Hh, N = 1920, 1080, 4
     C = rig.camera_models(N, W, Hh, seed=0)
     frames = rig.world_frames(C, W, Hh, 3, seed=0, world_fn=world)
+    args.lenses = None
+    if args.lens:
+        K, dist = bench_lens(W, Hh)
+        frames = raw_frames(frames, K, dist)
+        args.lenses = {c: (K, dist) for c in range(N)}
     if args.camera_scales:
         scales = [float(v) for v in args.camera_scales.split(",")]
         if len(scales) != N:
@@ -205,7 +253,7 @@ def main():
                                "Hamming kNN-2, ratio 0.75; RANSAC 3.0 px, 2000 hypotheses; 3 "
                                "adjacent pairs" % args.nfeatures,
                    "host_frames": "pinned" if args.pinned else "pageable",
-                   "host_threads": args.threads},
+                   "lens": bool(args.lens), "host_threads": args.threads},
         "stage_ms_per_capture": {k: round(v / args.steps * 1e3, 3) for k, v in tot.items()},
         "keypoints": res[0][3], "matches": [r[1] for r in res], "inliers": [r[2] for r in res],
         "max_reproj_err_px_vs_truth": errs,
@@ -236,7 +284,7 @@ def stitch_main(args, frames, truth, W, Hh, N):
     pitch = 8192 * 3
     out = torch.empty((2048, pitch), dtype=torch.uint8, device=dev)
     est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
-                                    blend=BLENDS[args.blend])
+                                    blend=BLENDS[args.blend], lenses=args.lenses)
     ptrs = [t.data_ptr() for t in d]
     tot = {"upload": 0.0, "estimate": 0.0, "plan_stitch": 0.0}
     mpix = 0.0
@@ -269,7 +317,7 @@ def stitch_main(args, frames, truth, W, Hh, N):
     pair_H, plan = capture(False)
     ow, oh = plan.out_w, plan.out_h
     got = out[:oh, :ow * 3].cpu().numpy().reshape(oh, ow, 3)
-    want = cpu_render(oracle, plan, frames, args.blend)
+    want = None if args.lens else cpu_render(oracle, plan, frames, args.blend)
     plan.close()
     est.close()
     errs = [pair_error(h, T, W, Hh) if h is not None else None for h, T in zip(pair_H, truth)]
@@ -287,12 +335,12 @@ def stitch_main(args, frames, truth, W, Hh, N):
                                "(in Python); mcs_stitch_direct (%s)" % (
                                    args.nfeatures, BLEND_NAMES[args.blend]),
                    "host_frames": "pageable, uploaded every capture",
-                   "host_threads": args.threads},
+                   "lens": bool(args.lens), "host_threads": args.threads},
         "stage_ms_per_capture": {k: round(v / args.steps * 1e3, 3) for k, v in tot.items()},
         "keypoints": est.stats.get("keypoints"), "matches": est.stats.get("matches"),
         "inliers": est.stats.get("inliers"), "max_reproj_err_px_vs_truth": errs,
-        "max_abs_diff_vs_cpu_render": int(np.abs(got.astype(np.int16) -
-                                                 want.astype(np.int16)).max()),
+        "max_abs_diff_vs_cpu_render": None if want is None else
+        int(np.abs(got.astype(np.int16) - want.astype(np.int16)).max()),
     }))
 
 
@@ -336,7 +384,7 @@ def pipelined_main(args, frames, truth, W, Hh, N):
         e.record(sts[0])
     est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
                                     captures_per_job=B, blend=BLENDS[args.blend],
-                                    exposure=args.exposure)
+                                    exposure=args.exposure, lenses=args.lenses)
     pending = [None] * D          # plan of the capture last stitched from frame set / output i
     lat = []
 
@@ -431,8 +479,8 @@ def pipelined_main(args, frames, truth, W, Hh, N):
             link = reps * sum(h.numel() for h in host) / (time.perf_counter() - tl) / 1e9
     ow, oh = plan.out_w, plan.out_h
     got = out[slot][:oh, :ow * 3].cpu().numpy().reshape(oh, ow, 3)
-    want = cpu_render(oracle, plan, frames, args.blend,
-                      est.gains_q if args.exposure is not None else None)
+    want = None if args.lens else cpu_render(
+        oracle, plan, frames, args.blend, est.gains_q if args.exposure is not None else None)
     for q in pending:
         if q is not None:
             q.close()
@@ -459,7 +507,7 @@ def pipelined_main(args, frames, truth, W, Hh, N):
                    "exposure_step_log2": args.exposure, "camera_scales": args.camera_scales,
                    "exposure_gains_last_capture": [round(float(g), 6) for g in est.gains]
                    if args.exposure is not None else None,
-                   "host_threads": args.threads},
+                   "lens": bool(args.lens), "host_threads": args.threads},
         "frames_resident_in_hbm": bool(args.resident),
         "h2d_gb_per_s": None if link is None else
         round(captures * sum(h.numel() for h in host) / elapsed / 1e9, 2),
@@ -469,7 +517,8 @@ def pipelined_main(args, frames, truth, W, Hh, N):
         "latency_ms_upload_to_homographies": round(float(np.mean(lat)) * 1e3, 3),
         "keypoints": est.stats.get("keypoints"), "matches": est.stats.get("matches"),
         "inliers": est.stats.get("inliers"), "max_reproj_err_px_vs_truth": errs,
-        "max_abs_diff_vs_cpu_render": int(np.abs(got.astype(np.int16) - want).max()),
+        "max_abs_diff_vs_cpu_render": None if want is None else
+        int(np.abs(got.astype(np.int16) - want).max()),
     }))
 
 

@@ -22,6 +22,10 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+# the bench's mild lens (also tools/estimate_bench.py --lens)
+FOCAL = 1100.0
+DIST = (-0.12, 0.03, 0.0, 0.0)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -30,8 +34,8 @@ def main():
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
-    ap.add_argument("--focal", type=float, default=1100.0)
-    ap.add_argument("--dist", type=float, nargs="*", default=[-0.12, 0.03, 0.0, 0.0])
+    ap.add_argument("--focal", type=float, default=FOCAL)
+    ap.add_argument("--dist", type=float, nargs="*", default=list(DIST))
     ap.add_argument("--blend", choices=["multiband", "feather", "seam", "none"],
                     default="multiband", help="seam / none: the streaming launch alone")
     ap.add_argument("--out", default=None)
