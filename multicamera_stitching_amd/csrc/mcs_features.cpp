@@ -145,6 +145,18 @@ int mcs::feat::launch(const Api *A, hipFunction_t f, unsigned gx, unsigned gy, u
     return MCS_OK;
 }
 
+mcs::feat::KnnShape mcs::feat::knn_shape(int queries, int pairs, int train)
+{
+    KnnShape k = {};
+    k.qblocks = (unsigned)((queries + kKnnQueriesPerBlock - 1) / kKnnQueriesPerBlock);
+    const int blocks = (int)k.qblocks * pairs;
+    int chunks = (kKnnTargetBlocks + blocks - 1) / blocks;
+    chunks = std::max(1, std::min(chunks, (train + 63) / 64));
+    k.per_chunk = (train + chunks - 1) / chunks;
+    k.chunks = train > 0 ? (unsigned)((train + k.per_chunk - 1) / k.per_chunk) : 0u;
+    return k;
+}
+
 namespace {
 
 int knn2(const Api *A, const FeatureKernels *k, const uint8_t *q, int nq, const uint8_t *t, int nt,
@@ -159,20 +171,13 @@ int knn2(const Api *A, const FeatureKernels *k, const uint8_t *q, int nq, const 
     a.nq = nq;
     a.nt = nt;
     a.pad_ = 0;
-    // enough (query wave x train chunk) blocks to fill the chip twice over (16384 waves: 16 per
-    // SIMD, the compare loop's LDS-read latency needs them; 4096 left waves waiting on it half
-    // their cycles) with chunks of >= 64 descriptors (3 atomics per query and chunk)
-    const int qblocks = (nq + mcs::kKnnQueriesPerBlock - 1) / mcs::kKnnQueriesPerBlock;
-    int chunks = (mcs::kKnnTargetBlocks + qblocks - 1) / qblocks;
-    chunks = std::max(1, std::min(chunks, (nt + 63) / 64));
-    a.per_chunk = (nt + chunks - 1) / chunks;
-    chunks = nt > 0 ? (nt + a.per_chunk - 1) / a.per_chunk : 0;
-    int rc = MCS_OK;
-    if (chunks > 0)
-        rc = launch(A, k->knn2, qblocks, chunks, mcs::kKnnLanes, &a, sizeof(a), s);
-    if (rc == MCS_OK)
-        rc = launch(A, k->knn2_finalize, (2 * nq + 255) / 256, 1, 256, &a, sizeof(a), s);
-    return rc;
+    const mcs::feat::KnnShape ks = mcs::feat::knn_shape(nq, 1, nt);
+    a.per_chunk = ks.per_chunk;
+    if (ks.chunks > 0) {
+        const int rc = launch(A, k->knn2, ks.qblocks, ks.chunks, mcs::kKnnLanes, &a, sizeof(a), s);
+        if (rc) return rc;
+    }
+    return launch(A, k->knn2_finalize, (2 * nq + 255) / 256, 1, 256, &a, sizeof(a), s);
 }
 
 // L2 kNN-2 on device buffers (float descriptors); scratch allocated here; synchronises.
@@ -285,6 +290,82 @@ int check_sizes(int nq, int nt)
     return MCS_OK;
 }
 
+// The status of a per-call entry point's body on workspace stream s.  A failed body first drains
+// the stream: it may have queued copies from or towards host memory that the entry point, or its
+// caller on seeing the status, is about to release.
+int drained(const Api *A, hipStream_t s, int rc)
+{
+    if (rc) (void)ws_sync(A, s);
+    return rc;
+}
+
+// mcs_match_hamming_knn2_host on its workspace (buf, s), after the checks.
+int knn2_host(const Api *A, const FeatureKernels *k, uint8_t *buf, hipStream_t s,
+              const uint8_t *query, int n_query, const uint8_t *train, int n_train, int32_t *idx2,
+              int32_t *dist2)
+{
+    static const char what[] = "knn2 host path";
+    const size_t qb = (size_t)n_query * mcs::kDescBytes, tb = (size_t)n_train * mcs::kDescBytes;
+    const size_t ob = (size_t)n_query * 2 * sizeof(int32_t);
+    uint8_t *dq = buf, *dt = buf + qb;
+    int32_t *di = reinterpret_cast<int32_t *>(buf + ((qb + tb + 15) & ~(size_t)15));
+    int32_t *dd = di + (size_t)n_query * 2;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(dq, query, qb, hipMemcpyHostToDevice, s));
+    if (tb) HIP_TRY_AS(what, A->hipMemcpyAsync(dt, train, tb, hipMemcpyHostToDevice, s));
+    const int rc = knn2(A, k, dq, n_query, dt, n_train, di, dd, s);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(idx2, di, ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(dist2, dd, ob, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, ws_sync(A, s));
+    return MCS_OK;
+}
+
+// mcs_ransac_homography_host's host temporaries (they outlive the body: see drained).
+struct RansacHost {
+    std::vector<double> pts;        // n x (x, y, u, v)
+    std::vector<int32_t> scores;    // per hypothesis
+    std::vector<uint8_t> mask;      // the best model's inliers
+    double h8[8] = {0};             // the best model
+    int best_score = -1;
+};
+
+// mcs_ransac_homography_host on its workspace, after the checks: the best hypothesis (the first
+// of the maximum score) and, when it has the 4 inliers a model needs, its mask and model into `t`.
+int ransac_host(const Api *A, const FeatureKernels *k, uint8_t *buf, hipStream_t s, int n,
+                double thresh, int iters, uint32_t seed, RansacHost &t)
+{
+    static const char what[] = "ransac";
+    const size_t pb = t.pts.size() * sizeof(double), hb = (size_t)iters * 8 * sizeof(double);
+    const size_t sb = (size_t)iters * sizeof(int32_t);
+    mcs::KRansacArgs a;
+    a.pts = reinterpret_cast<double *>(buf);
+    a.hyps = reinterpret_cast<double *>(buf + pb);
+    a.scores = reinterpret_cast<int32_t *>(buf + pb + hb);
+    a.mask = buf + pb + hb + sb;
+    a.t2 = thresh * thresh;
+    a.n = n;
+    a.iters = iters;
+    a.best = 0;
+    a.seed = seed;
+    HIP_TRY_AS(what, A->hipMemcpyAsync((void *)a.pts, t.pts.data(), pb, hipMemcpyHostToDevice, s));
+    int rc = launch(A, k->ransac_score, iters, 1, mcs::kRansacBlock, &a, sizeof(a), s);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(t.scores.data(), a.scores, sb, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, ws_sync(A, s));
+    int best = -1;
+    for (int i = 0; i < iters; i++)
+        if (t.scores[i] > t.best_score) t.best_score = t.scores[i], best = i;
+    if (t.best_score < 4) return MCS_OK;
+    a.best = best;
+    rc = launch(A, k->ransac_mask, (n + 255) / 256, 1, 256, &a, sizeof(a), s);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(t.mask.data(), a.mask, (size_t)n, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(t.h8, a.hyps + (size_t)best * 8, sizeof(t.h8),
+                                       hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, ws_sync(A, s));
+    return MCS_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -321,25 +402,13 @@ int mcs_match_hamming_knn2_host(const uint8_t *query, int n_query, const uint8_t
     const FeatureKernels *k = nullptr;
     rc = feature_kernels(A, device, &k);
     if (rc) return rc;
-    const size_t qb = (size_t)n_query * mcs::kDescBytes, tb = (size_t)n_train * mcs::kDescBytes;
-    const size_t ob = (size_t)n_query * 2 * sizeof(int32_t);
     uint8_t *buf = nullptr;
     hipStream_t s = nullptr;
-    rc = workspace(A, device, qb + tb + 2 * ob + 64, &buf, &s);
+    // (both descriptor sets, then idx2 and dist2: knn2_host)
+    rc = workspace(A, device, ((size_t)n_query + n_train) * mcs::kDescBytes +
+                                  (size_t)n_query * 4 * sizeof(int32_t) + 64, &buf, &s);
     if (rc) return rc;
-    uint8_t *dq = buf, *dt = buf + qb;
-    int32_t *di = reinterpret_cast<int32_t *>(buf + ((qb + tb + 15) & ~(size_t)15));
-    int32_t *dd = di + (size_t)n_query * 2;
-    hipError_t e = A->hipMemcpyAsync(dq, query, qb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && tb) e = A->hipMemcpyAsync(dt, train, tb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) rc = knn2(A, k, dq, n_query, dt, n_train, di, dd, s);
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(idx2, di, ob, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(dist2, dd, ob, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = ws_sync(A, s);
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "knn2 host path: %s", A->hipGetErrorString(e));
-    return rc;
+    return drained(A, s, knn2_host(A, k, buf, s, query, n_query, train, n_train, idx2, dist2));
 }
 
 int mcs_match_l2_knn2(const float *d_query, int n_query, const float *d_train, int n_train,
@@ -400,62 +469,29 @@ int mcs_ransac_homography_host(const float *src_xy, const float *dst_xy, int n, 
     const FeatureKernels *k = nullptr;
     int rc = feature_kernels(A, device, &k);
     if (rc) return rc;
-    std::vector<double> pts((size_t)n * 4);
+    RansacHost t;
+    t.pts.resize((size_t)n * 4);
     for (int i = 0; i < n; i++) {
-        pts[4 * i] = src_xy[2 * i], pts[4 * i + 1] = src_xy[2 * i + 1];
-        pts[4 * i + 2] = dst_xy[2 * i], pts[4 * i + 3] = dst_xy[2 * i + 1];
+        t.pts[4 * i] = src_xy[2 * i], t.pts[4 * i + 1] = src_xy[2 * i + 1];
+        t.pts[4 * i + 2] = dst_xy[2 * i], t.pts[4 * i + 3] = dst_xy[2 * i + 1];
     }
-    const size_t pb = pts.size() * sizeof(double), hb = (size_t)iters * 8 * sizeof(double);
-    const size_t sb = (size_t)iters * sizeof(int32_t);
+    t.scores.resize((size_t)iters);
+    t.mask.resize((size_t)n);
     uint8_t *buf = nullptr;
     hipStream_t s = nullptr;
-    rc = workspace(A, device, pb + hb + sb + (size_t)n + 64, &buf, &s);
+    rc = workspace(A, device, t.pts.size() * sizeof(double) + (size_t)iters * 8 * sizeof(double) +
+                                  (size_t)iters * sizeof(int32_t) + (size_t)n + 64, &buf, &s);
     if (rc) return rc;
-    mcs::KRansacArgs a;
-    a.pts = reinterpret_cast<double *>(buf);
-    a.hyps = reinterpret_cast<double *>(buf + pb);
-    a.scores = reinterpret_cast<int32_t *>(buf + pb + hb);
-    a.mask = buf + pb + hb + sb;
-    a.t2 = thresh * thresh;
-    a.n = n;
-    a.iters = iters;
-    a.best = 0;
-    a.seed = seed;
-    std::vector<int32_t> scores((size_t)iters);
-    std::vector<uint8_t> m8((size_t)n);
-    double hb8[8];
-    hipError_t e = A->hipMemcpyAsync((void *)a.pts, pts.data(), pb, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess)
-        rc = launch(A, k->ransac_score, iters, 1, mcs::kRansacBlock, &a, sizeof(a), s);
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(scores.data(), a.scores, sb, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == MCS_OK) e = ws_sync(A, s);
-    int best = -1, best_score = -1;
-    if (e == hipSuccess && rc == MCS_OK) {
-        for (int i = 0; i < iters; i++)
-            if (scores[i] > best_score) best_score = scores[i], best = i;
-        if (best_score >= 4) {
-            a.best = best;
-            rc = launch(A, k->ransac_mask, (n + 255) / 256, 1, 256, &a, sizeof(a), s);
-            if (rc == MCS_OK)
-                e = A->hipMemcpyAsync(m8.data(), a.mask, (size_t)n, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && rc == MCS_OK)
-                e = A->hipMemcpyAsync(hb8, a.hyps + (size_t)best * 8, sizeof(hb8),
-                                      hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && rc == MCS_OK) e = ws_sync(A, s);
-        }
-    }
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "ransac: %s", A->hipGetErrorString(e));
-    if (rc) return rc;
-    if (best_score < 4) return MCS_OK;
+    rc = drained(A, s, ransac_host(A, k, buf, s, n, thresh, iters, seed, t));
+    if (rc || t.best_score < 4) return rc;
     // findHomography's refinement of the chosen model on its inliers (mcs_refine.cpp:
     // normalised DLT re-estimate + Levenberg-Marquardt, StitcherClass.py:443-444)
-    for (int i = 0; i < 8; i++) H[i] = hb8[i];
+    for (int i = 0; i < 8; i++) H[i] = t.h8[i];
     H[8] = 1.0;
-    mcs::homography_refine(src_xy, dst_xy, n, m8.data(), H);
-    *n_inliers = best_score;
+    mcs::homography_refine(src_xy, dst_xy, n, t.mask.data(), H);
+    *n_inliers = t.best_score;
     if (mask)
-        for (int i = 0; i < n; i++) mask[i] = m8[i];
+        for (int i = 0; i < n; i++) mask[i] = t.mask[i];
     return MCS_OK;
 }
 
@@ -553,7 +589,195 @@ int mcs::feat::orb_geom(int w, int h, int nfeatures, int nlevels, float scale_fa
     return MCS_OK;
 }
 
+void mcs::feat::orb_chain(OrbChain *c, int w, int h, int fast_threshold, int n_frames,
+                          const OrbBuffers &b)
+{
+    const OrbGeom &g = c->geo;
+    const int L = g.nlevels;
+    const int64_t pix = (int64_t)g.off[L];
+    c->w = w, c->h = h, c->n_frames = n_frames;
+    const int K = c->K = std::max(g.n_bound, 1);
+    std::memset(&c->ga, 0, sizeof(c->ga));
+    c->ga.gray = b.lvl, c->ga.stride = pix, c->ga.n = w * h;
+    // levels 1 .. nlevels-1: one launch (mcs_orb_pyramid) when every level is a < 2x downscale of
+    // the one before (its blocks' dependency regions then tile every level), else a resize each
+    c->pyr_blocks = pyramid_args(g, b.lvl, c->ba);
+    c->ba.stride = pix;
+    // blur, FAST, NMS and Harris of every level: one launch (kOrbTileW x kOrbTileH tiles); then
+    // the ranking on the device: a level with more than kOrbSelMax candidates sets the frame's
+    // overflow flag instead (sel[1]; the per-call entry point then ranks on the host)
+    KOrbPyrArgs &pa = c->pa;
+    KOrbSelArgs &sa = c->sa;
+    std::memset(&pa, 0, sizeof(pa));
+    std::memset(&sa, 0, sizeof(sa));
+    pa.img = b.lvl, pa.blur = b.blur;
+    pa.cand = b.cand, sa.cand = b.cand;
+    pa.ncand = b.ncand, sa.ncand = b.ncand;
+    pa.nlevels = sa.nlevels = L;
+    pa.threshold = fast_threshold;
+    pa.stride = pix;
+    pa.cstride = sa.cstride = (int)g.cap_total;
+    sa.kp = b.kp, sa.resp = b.resp, sa.sel = b.sel, sa.kstride = K;
+    for (int l = 0; l < L; l++) {
+        pa.off[l] = (int64_t)g.off[l];
+        pa.coff[l] = sa.coff[l] = (int)g.coff[l];
+        pa.w[l] = g.lw[l];
+        pa.h[l] = g.lh[l];
+        pa.cap[l] = sa.cap[l] = (int)g.cap[l];
+        pa.bstart[l + 1] = pa.bstart[l] + (g.lw[l] + kOrbTileW - 1) / kOrbTileW *
+                                              ((g.lh[l] + kOrbTileH - 1) / kOrbTileH);
+        sa.quota[l] = g.quota[l];
+    }
+    KOrbDescArgs &da = c->da;
+    std::memset(&da, 0, sizeof(da));
+    for (int l = 0; l < kOrbMaxLevels; l++) {
+        const int ll = l < L ? l : 0;
+        da.img[l] = b.lvl + g.off[ll];
+        da.blur[l] = b.blur + g.off[ll];
+        da.w[l] = g.lw[ll];
+    }
+    da.kp = b.kp, da.desc = b.desc, da.orient = b.orient, da.sel = b.sel;
+    da.n = g.n_bound, da.kstride = K, da.stride = pix;
+}
+
+int mcs::feat::orb_enqueue(const Api *A, const FeatureKernels *k, OrbChain &c,
+                           const uint8_t *const *frames, int channels, int device, hipStream_t s)
+{
+    const OrbGeom &g = c.geo;
+    const int C = c.n_frames, L = g.nlevels;
+    const int64_t pix = (int64_t)g.off[L];
+    int rc = MCS_OK;
+    if (channels == 3) {
+        for (int f = 0; f < C; f++) c.ga.bgr[f] = frames[f];
+        rc = launch(A, k->orb_gray, (unsigned)((c.w * c.h + 1023) / 1024), C, 256, &c.ga,
+                    sizeof(c.ga), s);
+        if (rc) return rc;
+    } else {
+        for (int f = 0; f < C; f++)
+            HIP_TRY_AS("orb", A->hipMemcpyAsync(c.ga.gray + f * pix, frames[f],
+                                                (size_t)c.w * c.h, hipMemcpyDeviceToDevice, s));
+    }
+    if (L > 1 && c.pyr_blocks > 0) {
+        rc = launch(A, k->orb_pyramid, c.pyr_blocks, C, 256, &c.ba, sizeof(c.ba), s, 1,
+                    (unsigned)(2 * c.ba.lds_w * c.ba.lds_h + 16));
+        if (rc) return rc;
+    } else {
+        for (int l = 1; l < L; l++) {
+            rc = mcs_resize_linear_device(c.ga.gray + g.off[l - 1], g.lw[l - 1], g.lh[l - 1],
+                                          g.lw[l - 1], pix, c.ga.gray + g.off[l], g.lw[l], g.lh[l],
+                                          g.lw[l], pix, 1, C, device, s);
+            if (rc) return rc;
+        }
+    }
+    rc = launch(A, k->orb_level, (unsigned)c.pa.bstart[L], C, kOrbLevelThreads, &c.pa,
+                sizeof(c.pa), s);
+    if (rc) return rc;
+    rc = launch(A, k->orb_select, (unsigned)L, C, kOrbSelThreads, &c.sa, sizeof(c.sa), s);
+    if (rc) return rc;
+    if (g.n_bound > 0)
+        rc = launch(A, k->orb_describe, (unsigned)g.n_bound, C, 64, &c.da, sizeof(c.da), s);
+    return rc;
+}
+
 namespace {
+
+// orb_detect's host results (they outlive the body: see drained).
+struct OrbHost {
+    std::vector<int> kp;             // n x (level, x, y)
+    std::vector<double> orient;      // n x (cos, sin)
+    std::vector<double> resp;
+    int n = 0;
+};
+
+// orb_detect on its workspace stream s, after the checks: the frame (uploaded to `upload` unless
+// that is NULL: it lies on the device), the chain, then ONE copy back of [b.ncand, + back_bytes):
+// counts, keypoints, descriptors, orientations, responses and the ranking's [n, overflow].  On
+// overflow the host ranks and the chain's describe launch runs again on its keypoints.
+int orb_host(const Api *A, const FeatureKernels *k, mcs::feat::OrbChain &ch,
+             const mcs::feat::OrbBuffers &b, uint8_t *upload, size_t back_bytes,
+             const uint8_t *image, int channels, int device, hipStream_t s, OrbHost &t,
+             uint8_t *desc)
+{
+    static const char what[] = "orb";
+    const mcs::feat::OrbGeom &g = ch.geo;
+    const int nlevels = g.nlevels;
+    const uint8_t *in = image;
+    if (upload) {
+        HIP_TRY_AS(what, A->hipMemcpyAsync(upload, image, (size_t)ch.w * ch.h * channels,
+                                           hipMemcpyHostToDevice, s));
+        in = upload;
+    }
+    HIP_TRY_AS(what, A->hipMemsetAsync(b.ncand, 0, mcs::kOrbMaxLevels * sizeof(int), s));
+    int rc = mcs::feat::orb_enqueue(A, k, ch, &in, channels, device, s);
+    if (rc) return rc;
+    static thread_local std::vector<uint8_t> blob;
+    if (blob.size() < back_bytes) blob.resize(back_bytes);
+    const uint8_t *dev0 = reinterpret_cast<const uint8_t *>(b.ncand);
+    auto at = [&](const void *d) { return blob.data() + (static_cast<const uint8_t *>(d) - dev0); };
+    HIP_TRY_AS(what, A->hipMemcpyAsync(blob.data(), dev0, back_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, ws_sync(A, s));
+    const int *sel = reinterpret_cast<const int *>(at(b.sel));
+    if (!sel[1]) {
+        const size_t n = t.n = sel[0];
+        const int *kpd = reinterpret_cast<const int *>(at(b.kp));
+        const double *respd = reinterpret_cast<const double *>(at(b.resp));
+        const double *ord = reinterpret_cast<const double *>(at(b.orient));
+        t.kp.assign(kpd, kpd + 3 * n);
+        t.resp.assign(respd, respd + n);
+        t.orient.assign(ord, ord + 2 * n);
+        std::memcpy(desc, at(b.desc), n * 32);
+        return MCS_OK;
+    }
+    // host ranking: only the candidates each level found come back (the host copy: per thread,
+    // grown on demand, never cleared -- only the entries the counts cover are copied and read)
+    static thread_local std::vector<mcs::OrbCand> cand;
+    if (cand.size() < g.cap_total) cand.resize(g.cap_total);
+    int counts[mcs::kOrbMaxLevels];
+    for (int l = 0; l < nlevels; l++) {
+        counts[l] = std::min(std::max(reinterpret_cast<const int *>(blob.data())[l], 0),
+                             (int)g.cap[l]);
+        if (counts[l] > 0)
+            HIP_TRY_AS(what, A->hipMemcpyAsync(cand.data() + g.coff[l], b.cand + g.coff[l],
+                                               (size_t)counts[l] * sizeof(mcs::OrbCand),
+                                               hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY_AS(what, ws_sync(A, s));
+    // per level: rank by response (desc), then y, then x; keep the level's quota (a strict total
+    // order -- positions are unique -- so selecting the quota first and sorting only it gives the
+    // full sort's prefix)
+    for (int l = 0; l < nlevels; l++) {
+        const int c = counts[l];
+        mcs::OrbCand *lc = cand.data() + g.coff[l];
+        auto rank = [](const mcs::OrbCand &p, const mcs::OrbCand &q) {
+            if (p.response != q.response) return p.response > q.response;
+            return p.y != q.y ? p.y < q.y : p.x < q.x;
+        };
+        const int keep = std::min(c, g.quota[l]);
+        if (keep < c) std::nth_element(lc, lc + keep, lc + c, rank);
+        std::sort(lc, lc + keep, rank);
+        for (int i = 0; i < keep; i++) {
+            t.kp.push_back(l);
+            t.kp.push_back(lc[i].x);
+            t.kp.push_back(lc[i].y);
+            t.resp.push_back(lc[i].response);
+        }
+    }
+    const int n = t.n = (int)t.kp.size() / 3;
+    t.orient.resize(2 * (size_t)std::max(n, 1));
+    if (n == 0) return MCS_OK;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(b.kp, t.kp.data(), t.kp.size() * sizeof(int),
+                                       hipMemcpyHostToDevice, s));
+    ch.da.sel = nullptr;
+    ch.da.n = n;
+    rc = launch(A, k->orb_describe, n, 1, 64, &ch.da, sizeof(ch.da), s);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(desc, b.desc, (size_t)n * 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(t.orient.data(), b.orient, (size_t)n * 2 * sizeof(double),
+                                       hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, ws_sync(A, s));
+    return MCS_OK;
+}
+
 // ORB of one image (host memory, or device memory when on_device); mcs_orb_detect_host /
 // mcs_orb_detect_device below.
 int orb_detect(const uint8_t *image, bool on_device, int w, int h, int channels, int nfeatures,
@@ -578,24 +802,20 @@ int orb_detect(const uint8_t *image, bool on_device, int w, int h, int channels,
     int rc = feature_kernels(A, device, &k);
     if (rc) return rc;
     // level sizes and quotas, as OpenCV's ORB computes them (float arithmetic)
-    mcs::feat::OrbGeom geo;
-    rc = mcs::feat::orb_geom(w, h, nfeatures, nlevels, scale_factor, &geo);
+    mcs::feat::OrbChain ch;
+    rc = mcs::feat::orb_geom(w, h, nfeatures, nlevels, scale_factor, &ch.geo);
     if (rc) return rc;
-    const int *lw = geo.lw, *lh = geo.lh, *quota = geo.quota;
-    const float *lscale = geo.lscale;
-    const size_t *off = geo.off, *cap = geo.cap, *coff = geo.coff;
-    const size_t pix = off[nlevels], cap_total = geo.cap_total;
+    const size_t pix = ch.geo.off[nlevels];
     // one allocation: input, levels, blur (u16 pass + u8), scores, candidates, counts, keypoints,
     // descriptors, orientations
-    const size_t in_bytes = (size_t)w * h * channels;
     size_t o = 0;
     auto take = [&](size_t bytes) {
         const size_t at = o;
         o += (bytes + 255) & ~(size_t)255;
         return at;
     };
-    const size_t o_in = take(in_bytes), o_lvl = take(pix), o_blur = take(pix);
-    const size_t o_cand = take(cap_total * sizeof(mcs::OrbCand));
+    const size_t o_in = take((size_t)w * h * channels), o_lvl = take(pix), o_blur = take(pix);
+    const size_t o_cand = take(ch.geo.cap_total * sizeof(mcs::OrbCand));
     const size_t o_cnt = take(mcs::kOrbMaxLevels * sizeof(int));
     const size_t o_kp = take((size_t)std::max(nfeatures, 1) * 3 * sizeof(int));
     const size_t o_desc = take((size_t)std::max(nfeatures, 1) * 32);
@@ -607,189 +827,29 @@ int orb_detect(const uint8_t *image, bool on_device, int w, int h, int channels,
     hipStream_t s = nullptr;
     rc = workspace(A, device, o, &buf, &s);
     if (rc) return rc;
-    std::vector<int> counts(nlevels);
-    // host copy of the candidates: per thread, grown on demand, never cleared (only the
-    // entries the counts cover are copied and read)
-    static thread_local std::vector<mcs::OrbCand> cand;
-    if (cand.size() < cap_total) cand.resize(cap_total);
-    std::vector<int> kp;
-    std::vector<double> orient, resp;
-    uint8_t *lvl0 = buf + o_lvl;
-    // the frame: uploaded into the workspace, or read where it lies on the device
-    const uint8_t *in = on_device ? image : buf + o_in;
-    hipError_t e = on_device ? hipSuccess
-                             : A->hipMemcpyAsync(buf + o_in, image, in_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = A->hipMemsetAsync(buf + o_cnt, 0, mcs::kOrbMaxLevels * sizeof(int), s);
-    if (e == hipSuccess) {
-        if (channels == 3) {
-            mcs::KGrayArgs ga;
-            std::memset(&ga, 0, sizeof(ga));
-            ga.bgr[0] = in;
-            ga.gray = lvl0;
-            ga.n = w * h;
-            rc = launch(A, k->orb_gray, (w * h + 1023) / 1024, 1, 256, &ga, sizeof(ga), s);
-        } else {
-            e = A->hipMemcpyAsync(lvl0, in, in_bytes, hipMemcpyDeviceToDevice, s);
-        }
-    }
-    // levels 1 .. nlevels-1: one launch (mcs_orb_pyramid) when every level is a < 2x
-    // downscale of the one before (its blocks' dependency regions then tile every level), else
-    // one resize launch per level
-    mcs::KOrbBuildArgs ba;
-    const unsigned pyr_blocks = e == hipSuccess && rc == MCS_OK && nlevels > 1
-                                    ? mcs::feat::pyramid_args(geo, buf + o_lvl, ba)
-                                    : 0u;
-    if (pyr_blocks > 0) {
-        size_t sz = sizeof(ba);
-        void *cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &ba, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz,
-                       HIP_LAUNCH_PARAM_END};
-        e = A->hipModuleLaunchKernel(k->orb_pyramid, pyr_blocks, 1, 1, 256, 1, 1,
-                                     (unsigned)(2 * ba.lds_w * ba.lds_h + 16), s, nullptr, cfg);
-    } else {
-        for (int l = 1; l < nlevels && e == hipSuccess && rc == MCS_OK; l++)
-            rc = mcs_resize_linear_device(buf + o_lvl + off[l - 1], lw[l - 1], lh[l - 1],
-                                          lw[l - 1], 0, buf + o_lvl + off[l], lw[l], lh[l], lw[l],
-                                          0, 1, 1, device, s);
-    }
-    if (e == hipSuccess && rc == MCS_OK) {
-        // blur, FAST, NMS and Harris of every level: one launch (mcs_orb_level, kOrbTileW x kOrbTileH tiles)
-        mcs::KOrbPyrArgs pa;
-        std::memset(&pa, 0, sizeof(pa));
-        pa.img = buf + o_lvl;
-        pa.blur = buf + o_blur;
-        pa.cand = reinterpret_cast<mcs::OrbCand *>(buf + o_cand);
-        pa.ncand = reinterpret_cast<int *>(buf + o_cnt);
-        pa.nlevels = nlevels;
-        pa.threshold = fast_threshold;
-        for (int l = 0; l < nlevels; l++) {
-            pa.off[l] = (int64_t)off[l];
-            pa.coff[l] = (int)coff[l];
-            pa.w[l] = lw[l];
-            pa.h[l] = lh[l];
-            pa.cap[l] = (int)cap[l];
-            pa.bstart[l + 1] = pa.bstart[l] + (lw[l] + mcs::kOrbTileW - 1) / mcs::kOrbTileW *
-                                            ((lh[l] + mcs::kOrbTileH - 1) / mcs::kOrbTileH);
-        }
-        rc = launch(A, k->orb_level, (unsigned)pa.bstart[nlevels], 1, mcs::kOrbLevelThreads, &pa,
-                    sizeof(pa), s);
-    }
-    // Device ranking (mcs_orb_select) and description, then ONE copy back of counts,
-    // keypoints, descriptors, orientations and responses.  A level with more than kOrbSelMax
-    // candidates sets the overflow flag instead; the host then ranks (below).
-    static thread_local std::vector<uint8_t> blob;
-    if (blob.size() < o_end - o_cnt) blob.resize(o_end - o_cnt);
-    auto at = [&](size_t off) { return blob.data() + (off - o_cnt); };
-    mcs::KOrbDescArgs da;
-    std::memset(&da, 0, sizeof(da));
-    for (int l = 0; l < mcs::kOrbMaxLevels; l++) {
-        const int ll = l < nlevels ? l : 0;
-        da.img[l] = buf + o_lvl + off[ll];
-        da.blur[l] = buf + o_blur + off[ll];
-        da.w[l] = lw[ll];
-    }
-    da.kp = reinterpret_cast<const int *>(buf + o_kp);
-    da.desc = buf + o_desc;
-    da.orient = reinterpret_cast<double *>(buf + o_or);
-    const int n_bound = geo.n_bound;
-    if (e == hipSuccess && rc == MCS_OK) {
-        mcs::KOrbSelArgs sa;
-        std::memset(&sa, 0, sizeof(sa));
-        sa.cand = reinterpret_cast<const mcs::OrbCand *>(buf + o_cand);
-        sa.ncand = reinterpret_cast<const int *>(buf + o_cnt);
-        sa.kp = reinterpret_cast<int *>(buf + o_kp);
-        sa.resp = reinterpret_cast<double *>(buf + o_resp);
-        sa.sel = reinterpret_cast<int *>(buf + o_sel);
-        for (int l = 0; l < nlevels; l++) {
-            sa.coff[l] = (int)coff[l];
-            sa.cap[l] = (int)cap[l];
-            sa.quota[l] = quota[l];
-        }
-        sa.nlevels = nlevels;
-        rc = launch(A, k->orb_select, (unsigned)nlevels, 1, mcs::kOrbSelThreads, &sa, sizeof(sa), s);
-        da.sel = sa.sel;
-        da.n = n_bound;
-        if (rc == MCS_OK && n_bound > 0)
-            rc = launch(A, k->orb_describe, (unsigned)n_bound, 1, 64, &da, sizeof(da), s);
-    }
-    if (e == hipSuccess && rc == MCS_OK)
-        e = A->hipMemcpyAsync(blob.data(), buf + o_cnt, o_end - o_cnt, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == MCS_OK) e = ws_sync(A, s);
-    int n = 0;
-    const int *sel = reinterpret_cast<const int *>(at(o_sel));
-    const int *kpd = reinterpret_cast<const int *>(at(o_kp));
-    const double *respd = reinterpret_cast<const double *>(at(o_resp));
-    const double *ord = reinterpret_cast<const double *>(at(o_or));
-    if (e == hipSuccess && rc == MCS_OK && !sel[1]) {
-        n = sel[0];
-        kp.assign(kpd, kpd + 3 * (size_t)n);
-        resp.assign(respd, respd + n);
-        orient.assign(ord, ord + 2 * (size_t)n);
-        std::memcpy(desc, at(o_desc), (size_t)n * 32);
-    } else if (e == hipSuccess && rc == MCS_OK) {
-        // host ranking: only the candidates each level found come back
-        std::memcpy(counts.data(), at(o_cnt), nlevels * sizeof(int));
-        for (int l = 0; l < nlevels && e == hipSuccess; l++) {
-            const int c = std::min(std::max(counts[l], 0), (int)cap[l]);
-            if (c > 0)
-                e = A->hipMemcpyAsync(cand.data() + coff[l],
-                                      buf + o_cand + coff[l] * sizeof(mcs::OrbCand),
-                                      (size_t)c * sizeof(mcs::OrbCand), hipMemcpyDeviceToHost, s);
-        }
-        if (e == hipSuccess) e = ws_sync(A, s);
-        if (e == hipSuccess) {
-            // per level: rank by response (desc), then y, then x; keep the level's quota (a
-            // strict total order -- positions are unique -- so selecting the quota first and
-            // sorting only it gives the full sort's prefix)
-            for (int l = 0; l < nlevels; l++) {
-                const int c = std::min(counts[l], (int)cap[l]);
-                mcs::OrbCand *b = cand.data() + coff[l];
-                auto rank = [](const mcs::OrbCand &p, const mcs::OrbCand &q) {
-                    if (p.response != q.response) return p.response > q.response;
-                    return p.y != q.y ? p.y < q.y : p.x < q.x;
-                };
-                const int keep = std::min(c, quota[l]);
-                if (keep < c) std::nth_element(b, b + keep, b + c, rank);
-                std::sort(b, b + keep, rank);
-                for (int i = 0; i < keep; i++) {
-                    kp.push_back(l);
-                    kp.push_back(b[i].x);
-                    kp.push_back(b[i].y);
-                    resp.push_back(b[i].response);
-                }
-            }
-            n = (int)kp.size() / 3;
-            orient.resize(2 * (size_t)std::max(n, 1));
-        }
-        if (e == hipSuccess && n > 0) {
-            e = A->hipMemcpyAsync(buf + o_kp, kp.data(), kp.size() * sizeof(int),
-                                  hipMemcpyHostToDevice, s);
-            da.sel = nullptr;
-            da.n = n;
-            if (e == hipSuccess) rc = launch(A, k->orb_describe, n, 1, 64, &da, sizeof(da), s);
-            if (e == hipSuccess && rc == MCS_OK)
-                e = A->hipMemcpyAsync(desc, buf + o_desc, (size_t)n * 32, hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && rc == MCS_OK)
-                e = A->hipMemcpyAsync(orient.data(), buf + o_or, (size_t)n * 2 * sizeof(double),
-                                      hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess && rc == MCS_OK) e = ws_sync(A, s);
-        }
-    }
-    if (e == hipSuccess && rc != MCS_OK) e = ws_sync(A, s);   // drain on error
-    if (e != hipSuccess) return mcs::fail(MCS_E_HIP, "orb: %s", A->hipGetErrorString(e));
+    const mcs::feat::OrbBuffers b = {
+        buf + o_lvl, buf + o_blur, reinterpret_cast<mcs::OrbCand *>(buf + o_cand),
+        reinterpret_cast<int *>(buf + o_cnt), reinterpret_cast<int *>(buf + o_kp),
+        reinterpret_cast<double *>(buf + o_resp), buf + o_desc,
+        reinterpret_cast<double *>(buf + o_or), reinterpret_cast<int *>(buf + o_sel)};
+    mcs::feat::orb_chain(&ch, w, h, fast_threshold, 1, b);
+    OrbHost t;
+    rc = drained(A, s, orb_host(A, k, ch, b, on_device ? nullptr : buf + o_in, o_end - o_cnt,
+                                image, channels, device, s, t, desc));
     if (rc) return rc;
-    for (int i = 0; i < n; i++) {
-        const int l = kp[3 * i];
-        kp_xy[2 * i] = (float)kp[3 * i + 1] * lscale[l];
-        kp_xy[2 * i + 1] = (float)kp[3 * i + 2] * lscale[l];
+    for (int i = 0; i < t.n; i++) {
+        const int l = t.kp[3 * i];
+        kp_xy[2 * i] = (float)t.kp[3 * i + 1] * ch.geo.lscale[l];
+        kp_xy[2 * i + 1] = (float)t.kp[3 * i + 2] * ch.geo.lscale[l];
         if (kp_level) kp_level[i] = l;
-        if (kp_response) kp_response[i] = (float)resp[i];
+        if (kp_response) kp_response[i] = (float)t.resp[i];
         if (kp_angle) {
-            double a = std::atan2(orient[2 * i + 1], orient[2 * i]) * (180.0 / M_PI);
+            double a = std::atan2(t.orient[2 * i + 1], t.orient[2 * i]) * (180.0 / M_PI);
             if (a < 0) a += 360.0;
             kp_angle[i] = (float)a;
         }
     }
-    *n_out = n;
+    *n_out = t.n;
     return MCS_OK;
 }
 }  // namespace

@@ -13,7 +13,7 @@
 // refinement (mcs_refine.cpp) per pair.  The same kernels and arithmetic as the per-call entry
 // points, so the same homographies, bit for bit.  The chain is captured once as a hipGraph and
 // replayed while the job is fed the same frame pointers (one graph launch per capture; a new
-// frame set re-captures it; MCS_RIG_GRAPH=0: plain launches).
+// frame set re-captures it).
 //
 // Per-call path (a capture whose ORB ranking overflowed on the device -- more than kOrbSelMax
 // candidates on a level --, or MCS_RIG_PATH=calls): the C-ABI's own steps
@@ -108,17 +108,11 @@ struct RigDevice {
     uint8_t *buf = nullptr;      // device: every per-capture buffer
     uint8_t *host = nullptr;     // pinned: the copy-back blob
     size_t blob_bytes = 0;
-    mcs::feat::OrbGeom geo;
-    int K = 0;                   // keypoints per camera at most (the quotas' sum)
-    unsigned pyr_blocks = 0, knn_qblocks = 0, knn_chunks = 0;
+    mcs::feat::OrbChain orb;     // the cameras' ORB (orb.K: keypoints per camera at most)
+    mcs::feat::KnnShape knn;
     size_t o_cnt = 0, cnt_bytes = 0, o_keys = 0, keys_bytes = 0, o_blob = 0;
     size_t o_sel = 0, o_info = 0, o_hbest = 0, o_mask = 0, o_pts = 0;   // within the blob
     size_t o_lens = 0, o_lpts = 0;   // the lens table (n_cams rows) and mcs_rig_unlens's positions
-    mcs::KGrayArgs ga;
-    mcs::KOrbBuildArgs ba;
-    mcs::KOrbPyrArgs pa;
-    mcs::KOrbSelArgs sa;
-    mcs::KOrbDescArgs da;
     mcs::KRigArgs ra;
     // the chain captured as a hipGraph for the frame pointers it was captured with (a job is
     // usually fed the same frame set every time: one per capture slot in flight)
@@ -278,26 +272,16 @@ void orb_task(mcs_rig_job *j, int c)
             Pool::get().run([j, k] { pair_task(j, k); });
 }
 
-const mcs::rt::Api *api_for(int device, int *rc)
-{
-    const mcs::rt::Api *A = mcs::rt::api();
-    *rc = A ? MCS_OK : MCS_E_HIP;
-    return A;
-}
-
 // Sizes, offsets, stream and buffers of the device path; the argument blocks that do not change
-// between captures.
-int device_setup(mcs_rig_job *j)
+// between captures (the ORB chain's: mcs::feat::orb_chain).
+int device_setup(mcs_rig_job *j, const mcs::rt::Api *A)
 {
     RigDevice &d = j->dev;
-    int rc = MCS_OK;
-    const mcs::rt::Api *A = api_for(j->device, &rc);
+    mcs::feat::OrbGeom &g = d.orb.geo;
+    const int rc = mcs::feat::orb_geom(j->w, j->h, j->nfeatures, j->nlevels, j->scale_factor, &g);
     if (rc) return rc;
-    rc = mcs::feat::orb_geom(j->w, j->h, j->nfeatures, j->nlevels, j->scale_factor, &d.geo);
-    if (rc) return rc;
-    const mcs::feat::OrbGeom &g = d.geo;
     const int C = j->ci, P = j->ci - 1, L = j->nlevels;
-    const int K = d.K = std::max(g.n_bound, 1);
+    const int K = std::max(g.n_bound, 1);
     const size_t pix = g.off[L];
     size_t o = 0;
     auto take = [&](size_t bytes) {
@@ -334,74 +318,22 @@ int device_setup(mcs_rig_job *j)
     d.o_pts = btake((size_t)P * K * 4 * sizeof(double));
     d.blob_bytes = b;
     o += b;
-    const mcs::Entry on_device(j->device);
-    if (on_device.status) return on_device.status;
     HIP_TRY(A->hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking));
     HIP_TRY(A->hipMalloc((void **)&d.buf, o));
     HIP_TRY(A->hipHostMalloc((void **)&d.host, d.blob_bytes, 0));
     uint8_t *B = d.buf, *blob = d.buf + d.o_blob;
-    int *sel = reinterpret_cast<int *>(blob + d.o_sel);
 
-    std::memset(&d.ga, 0, sizeof(d.ga));
-    d.ga.gray = B + o_lvl;
-    d.ga.stride = (int64_t)pix;
-    d.ga.n = j->w * j->h;
-    d.pyr_blocks = mcs::feat::pyramid_args(g, B + o_lvl, d.ba);
-    d.ba.stride = (int64_t)pix;
-
-    std::memset(&d.pa, 0, sizeof(d.pa));
-    d.pa.img = B + o_lvl;
-    d.pa.blur = B + o_blur;
-    d.pa.cand = reinterpret_cast<mcs::OrbCand *>(B + o_cand);
-    d.pa.ncand = reinterpret_cast<int *>(B + d.o_cnt);
-    d.pa.nlevels = L;
-    d.pa.threshold = j->fast_threshold;
-    d.pa.stride = (int64_t)pix;
-    d.pa.cstride = (int)g.cap_total;
-    for (int l = 0; l < L; l++) {
-        d.pa.off[l] = (int64_t)g.off[l];
-        d.pa.coff[l] = (int)g.coff[l];
-        d.pa.w[l] = g.lw[l];
-        d.pa.h[l] = g.lh[l];
-        d.pa.cap[l] = (int)g.cap[l];
-        d.pa.bstart[l + 1] = d.pa.bstart[l] + (g.lw[l] + mcs::kOrbTileW - 1) / mcs::kOrbTileW *
-                                                ((g.lh[l] + mcs::kOrbTileH - 1) / mcs::kOrbTileH);
-    }
-
-    std::memset(&d.sa, 0, sizeof(d.sa));
-    d.sa.cand = d.pa.cand;
-    d.sa.ncand = d.pa.ncand;
-    d.sa.kp = reinterpret_cast<int *>(B + o_kp);
-    d.sa.resp = reinterpret_cast<double *>(B + o_resp);
-    d.sa.sel = sel;
-    for (int l = 0; l < L; l++) {
-        d.sa.coff[l] = (int)g.coff[l];
-        d.sa.cap[l] = (int)g.cap[l];
-        d.sa.quota[l] = g.quota[l];
-    }
-    d.sa.nlevels = L;
-    d.sa.cstride = (int)g.cap_total;
-    d.sa.kstride = K;
-
-    std::memset(&d.da, 0, sizeof(d.da));
-    for (int l = 0; l < mcs::kOrbMaxLevels; l++) {
-        const int ll = l < L ? l : 0;
-        d.da.img[l] = B + o_lvl + g.off[ll];
-        d.da.blur[l] = B + o_blur + g.off[ll];
-        d.da.w[l] = g.lw[ll];
-    }
-    d.da.kp = d.sa.kp;
-    d.da.desc = B + o_desc;
-    d.da.orient = reinterpret_cast<double *>(B + o_or);
-    d.da.sel = sel;
-    d.da.n = g.n_bound;
-    d.da.kstride = K;
-    d.da.stride = (int64_t)pix;
+    const mcs::feat::OrbBuffers ob = {
+        B + o_lvl, B + o_blur, reinterpret_cast<mcs::OrbCand *>(B + o_cand),
+        reinterpret_cast<int *>(B + d.o_cnt), reinterpret_cast<int *>(B + o_kp),
+        reinterpret_cast<double *>(B + o_resp), B + o_desc,
+        reinterpret_cast<double *>(B + o_or), reinterpret_cast<int *>(blob + d.o_sel)};
+    mcs::feat::orb_chain(&d.orb, j->w, j->h, j->fast_threshold, C, ob);
 
     std::memset(&d.ra, 0, sizeof(d.ra));
-    d.ra.kp = d.sa.kp;
-    d.ra.desc = B + o_desc;
-    d.ra.sel = sel;
+    d.ra.kp = ob.kp;
+    d.ra.desc = ob.desc;
+    d.ra.sel = ob.sel;
     d.ra.keys = reinterpret_cast<uint32_t *>(B + d.o_keys);
     d.ra.pts = reinterpret_cast<double *>(blob + d.o_pts);
     d.ra.info = reinterpret_cast<int *>(blob + d.o_info);
@@ -418,13 +350,9 @@ int device_setup(mcs_rig_job *j)
     d.ra.lpts = reinterpret_cast<double *>(B + d.o_lpts);
     d.ra.n_cams = j->n_cams;
     j->lens_stale = true;   // (a fresh buffer: the table, if any, is uploaded before the chain)
-    // kNN-2 blocks: query waves x train chunks x pairs, enough to fill the chip (as the per-call
-    // matcher sizes them; the result does not depend on the chunking)
-    d.knn_qblocks = (unsigned)((K + mcs::kKnnQueriesPerBlock - 1) / mcs::kKnnQueriesPerBlock);
-    int chunks = (int)((mcs::kKnnTargetBlocks + d.knn_qblocks * P - 1) / (d.knn_qblocks * P));
-    chunks = std::max(1, std::min(chunks, (K + 63) / 64));
-    d.ra.per_chunk = (K + chunks - 1) / chunks;
-    d.knn_chunks = (unsigned)((K + d.ra.per_chunk - 1) / d.ra.per_chunk);
+    // kNN-2 blocks: query waves x train chunks x pairs (as the per-call matcher sizes them)
+    d.knn = mcs::feat::knn_shape(K, P, K);
+    d.ra.per_chunk = d.knn.per_chunk;
     d.ready = true;
     return MCS_OK;
 }
@@ -450,11 +378,8 @@ void device_release(mcs_rig_job *j)
 int exposure_buffers(mcs_rig_job *j)
 {
     if (j->d_stats && j->h_stats) return MCS_OK;
-    int rc = MCS_OK;
-    const mcs::rt::Api *A = api_for(j->device, &rc);
-    if (rc) return rc;
-    const mcs::Entry on_device(j->device);
-    if (on_device.status) return on_device.status;
+    const mcs::Entry A(j->device);
+    if (A.status) return A.status;
     const size_t bytes = (size_t)j->n_caps * 2 * j->n_cams * j->n_cams * sizeof(int64_t);
     if (!j->d_stats) HIP_TRY(A->hipMalloc((void **)&j->d_stats, bytes));
     if (!j->h_stats) HIP_TRY(A->hipHostMalloc((void **)&j->h_stats, bytes, 0));
@@ -480,52 +405,20 @@ int enqueue_chain(mcs_rig_job *j, const mcs::rt::Api *A, const mcs::feat::Featur
 {
     RigDevice &d = j->dev;
     using mcs::feat::launch;
-    const int C = j->ci, P = j->ci - 1, L = j->nlevels;
-    const mcs::feat::OrbGeom &g = d.geo;
-    const size_t pix = g.off[L];
-    int rc = MCS_OK;
-    if (j->channels == 3) {
-        for (int c = 0; c < C; c++) d.ga.bgr[c] = j->frames[c];
-        rc = launch(A, k->orb_gray, (unsigned)((j->w * j->h + 1023) / 1024), C, 256, &d.ga,
-                    sizeof(d.ga), s);
-    } else {
-        for (int c = 0; c < C; c++)
-            HIP_TRY(A->hipMemcpyAsync(d.ga.gray + c * pix, j->frames[c], (size_t)j->w * j->h,
-                                      hipMemcpyDeviceToDevice, s));
-    }
-    if (rc == MCS_OK && L > 1) {
-        if (d.pyr_blocks > 0) {
-            rc = launch(A, k->orb_pyramid, d.pyr_blocks, C, 256, &d.ba, sizeof(d.ba), s, 1,
-                        (unsigned)(2 * d.ba.lds_w * d.ba.lds_h + 16));
-        } else {
-            for (int l = 1; l < L && rc == MCS_OK; l++)
-                rc = mcs_resize_linear_device(d.ga.gray + g.off[l - 1], g.lw[l - 1], g.lh[l - 1],
-                                              g.lw[l - 1], (int64_t)pix, d.ga.gray + g.off[l],
-                                              g.lw[l], g.lh[l], g.lw[l], (int64_t)pix, 1, C,
-                                              j->device, s);
-        }
-    }
+    const unsigned P = (unsigned)(j->ci - 1), iters = (unsigned)j->iters;
+    int rc = mcs::feat::orb_enqueue(A, k, d.orb, j->frames.data(), j->channels, j->device, s);
     if (rc == MCS_OK)
-        rc = launch(A, k->orb_level, (unsigned)d.pa.bstart[L], C, mcs::kOrbLevelThreads, &d.pa,
-                    sizeof(d.pa), s);
-    if (rc == MCS_OK)
-        rc = launch(A, k->orb_select, (unsigned)L, C, mcs::kOrbSelThreads, &d.sa, sizeof(d.sa), s);
-    if (rc == MCS_OK && g.n_bound > 0)
-        rc = launch(A, k->orb_describe, (unsigned)g.n_bound, C, 64, &d.da, sizeof(d.da), s);
-    if (rc == MCS_OK)
-        rc = launch(A, k->rig_knn2, d.knn_qblocks, d.knn_chunks, mcs::kKnnLanes, &d.ra,
-                    sizeof(d.ra), s, (unsigned)P);
+        rc = launch(A, k->rig_knn2, d.knn.qblocks, d.knn.chunks, mcs::kKnnLanes, &d.ra,
+                    sizeof(d.ra), s, P);
     if (rc == MCS_OK && d.ra.lens)
-        rc = launch(A, k->rig_unlens, (unsigned)((d.K + 255) / 256), (unsigned)P, 256, &d.ra,
+        rc = launch(A, k->rig_unlens, (unsigned)((d.orb.K + 255) / 256), P, 256, &d.ra,
                     sizeof(d.ra), s);
-    if (rc == MCS_OK) rc = launch(A, k->rig_match, (unsigned)P, 1, 1024, &d.ra, sizeof(d.ra), s);
+    if (rc == MCS_OK) rc = launch(A, k->rig_match, P, 1, 1024, &d.ra, sizeof(d.ra), s);
     if (rc == MCS_OK)
-        rc = launch(A, k->rig_hyp, (unsigned)((j->iters + 63) / 64), (unsigned)P, 64, &d.ra,
-                    sizeof(d.ra), s);
+        rc = launch(A, k->rig_hyp, (iters + 63) / 64, P, 64, &d.ra, sizeof(d.ra), s);
     if (rc == MCS_OK)
-        rc = launch(A, k->rig_ransac, (unsigned)j->iters, (unsigned)P, mcs::kRansacBlock, &d.ra,
-                    sizeof(d.ra), s);
-    if (rc == MCS_OK) rc = launch(A, k->rig_best, (unsigned)P, 1, 1024, &d.ra, sizeof(d.ra), s);
+        rc = launch(A, k->rig_ransac, iters, P, mcs::kRansacBlock, &d.ra, sizeof(d.ra), s);
+    if (rc == MCS_OK) rc = launch(A, k->rig_best, P, 1, 1024, &d.ra, sizeof(d.ra), s);
     if (rc == MCS_OK)
         HIP_TRY(A->hipMemcpyAsync(d.host, d.buf + d.o_blob, d.blob_bytes, hipMemcpyDeviceToHost,
                                   s));
@@ -537,17 +430,15 @@ int enqueue_chain(mcs_rig_job *j, const mcs::rt::Api *A, const mcs::feat::Featur
 int device_capture(mcs_rig_job *j, bool *overflow)
 {
     *overflow = false;
+    const mcs::Entry A(j->device);
+    if (A.status) return A.status;
     int rc = MCS_OK;
-    const mcs::rt::Api *A = api_for(j->device, &rc);
-    if (rc) return rc;
-    if (!j->dev.ready && (rc = device_setup(j)) != MCS_OK) {
+    if (!j->dev.ready && (rc = device_setup(j, A)) != MCS_OK) {
         device_release(j);   // (a partial setup: the next capture starts from clean state)
         return rc;
     }
     RigDevice &d = j->dev;
     const mcs::feat::FeatureKernels *k = nullptr;
-    const mcs::Entry on_device(j->device);
-    if (on_device.status) return on_device.status;
     if ((rc = mcs::feat::feature_kernels(A, j->device, &k)) != MCS_OK) return rc;
     const int C = j->ci, P = j->ci - 1;
     hipStream_t s = d.s;
@@ -567,7 +458,7 @@ int device_capture(mcs_rig_job *j, bool *overflow)
         j->lens_stale = false;
     }
     if ((rc = enqueue_resets(j, A, s)) != MCS_OK) return rc;
-    if (d.pyr_blocks > 0) {
+    if (d.orb.pyr_blocks > 0) {
         if (!d.exec || d.graph_frames != j->frames) {
             if (d.exec) (void)A->hipGraphExecDestroy(d.exec);
             d.exec = nullptr;
@@ -606,6 +497,7 @@ int device_capture(mcs_rig_job *j, bool *overflow)
             return MCS_OK;
         }
     const int *info = reinterpret_cast<const int *>(d.host + d.o_info);
+    const size_t K = (size_t)d.orb.K;
     const double *hbest = reinterpret_cast<const double *>(d.host + d.o_hbest);
     for (int c = 0; c < C; c++) j->feat[c].n = sel[2 * c], j->feat[c].rc = MCS_OK;
     std::vector<float> src, dst;
@@ -620,7 +512,7 @@ int device_capture(mcs_rig_job *j, bool *overflow)
         if (nm <= 4 || score < 4) continue;
         // findHomography's refinement of the chosen model on its inliers (as
         // mcs_ransac_homography_host): the positions are floats carried as doubles
-        const double *pts = reinterpret_cast<const double *>(d.host + d.o_pts) + 4 * (size_t)p * d.K;
+        const double *pts = reinterpret_cast<const double *>(d.host + d.o_pts) + 4 * p * K;
         src.resize(2 * (size_t)nm);
         dst.resize(2 * (size_t)nm);
         for (int i = 0; i < nm; i++) {
@@ -629,7 +521,7 @@ int device_capture(mcs_rig_job *j, bool *overflow)
         }
         for (int i = 0; i < 8; i++) H[i] = hbest[8 * p + i];
         H[8] = 1.0;
-        mcs::homography_refine(src.data(), dst.data(), nm, d.host + d.o_mask + (size_t)p * d.K, H);
+        mcs::homography_refine(src.data(), dst.data(), nm, d.host + d.o_mask + p * K, H);
         j->n_inliers[p] = score;
         j->ok[p] = 1;
     }

@@ -394,6 +394,14 @@ def lattice_rig(dots=(0, 1, 2, 5, 40)):
 RIG_SMALL = [(160, 120, 2, 7), (160, 120, 2, 60), (320, 240, 2, 7), (320, 240, 2, 60),
              (320, 240, 4, 200), (320, 240, 7, 100)]
 RIG_TIED = [(320, 240, 4, 200), (320, 240, 7, 100)]
+# The rig job's per-level resize chain (3 levels at 2.0: no one-launch pyramid, so no graph either;
+# the resize runs with a frame stride over the cameras): (w, h, seed, nfeatures) of the smallest
+# 4:3 rig -- widths in steps of 16, seeds 0 .. 7 -- on which the oracle gives every camera keypoints
+# on two levels (level 1 is 96 x 72: 10 eligible rows) and every pair more than 4 matches; the
+# oracle's keypoints per camera and matches per pair.
+RIG_CHAIN = (192, 144, 4, 100)
+RIG_CHAIN_KEYPOINTS = [21, 29, 38]
+RIG_CHAIN_MATCHES = [5, 5]
 
 
 def opencv_gray(bgr):
@@ -401,12 +409,15 @@ def opencv_gray(bgr):
     return ((b[..., 0] * 1868 + b[..., 1] * 9617 + b[..., 2] * 4899 + 8192) >> 14).astype(np.uint8)
 
 
-def oracle_pairs(frames, nfeatures, nlevels, ratio=0.75):
+def oracle_pairs(frames, nfeatures, nlevels, ratio=0.75, scale_factor=1.2, levels=None):
     """The rig's estimation on the oracle as far as the matches: (keypoints per camera, per pair
-    (src, dst) float32 arrays of the ratio-tested matches, query camera k + 1 against train k)."""
+    (src, dst) float32 arrays of the ratio-tested matches, query camera k + 1 against train k).
+    levels: a list that receives the number of levels each camera has keypoints on."""
     from oracle import oracle
     feats = [oracle.orb_detect(f if f.ndim == 2 else opencv_gray(f), nfeatures=nfeatures,
-                               nlevels=nlevels) for f in frames]
+                               nlevels=nlevels, scale_factor=scale_factor) for f in frames]
+    if levels is not None:
+        levels[:] = [len(np.unique(f["level"])) for f in feats]
     pairs = []
     for k in range(len(frames) - 1):
         a, b = feats[k + 1], feats[k]

@@ -3,8 +3,15 @@
 // libmcs's host sources on the stub HIP runtime (stub_hip.h), driven through the C ABI only.
 // Five scenarios -- mcs_plan_find_seams, mcs_plan_footprint, mcs_seam_graphcut_device,
 // mcs_plan_overlap_stats with a table that is built, replaced and rebuilt after
-// mcs_plan_set_lens, and the L2 / Hamming host matchers -- on a 2-camera chain (64 x 48 x 3), a
-// 3-camera cylinder (96 x 32 x 1) and a plan with a 1 x 1 mosaic.  Per scenario:
+// mcs_plan_set_lens, and the L2 / Hamming host matchers with mcs_ransac_homography_host -- on a
+// 2-camera chain (64 x 48 x 3), a 3-camera cylinder (96 x 32 x 1) and a plan with a 1 x 1 mosaic.
+// Two more on the ORB launch chain (mcs_feat_int.h): `orb`, the per-call entry points on a
+// 64 x 48 frame (the one-launch pyramid, the resize chain, one level, and a device ranking
+// "overflow" that sends the call through host ranking); `rig`, rig jobs on the device path -- a
+// 3-camera job captured as a graph, replayed, and re-captured after mcs_rig_job_set_lens, then a
+// 2-capture batch job whose 2x pyramid takes plain launches.  The rig job's overflow fallback is
+// left out of the injection: it runs the per-call steps on pool threads, whose thread-lifetime
+// workspaces make the allocation snapshots depend on which thread ran what.  Per scenario:
 //   (a) a clean run, its log printed one event a line;
 //   (b) for k = 1 .. the clean run's runtime calls: call k fails.  The scenario returns a non-zero
 //       status; once the plans are destroyed, the device allocations, streams and pinned
@@ -14,7 +21,9 @@
 // release (release_tables) -- cannot make the call fail: such a k must leave MCS_OK and every
 // other event of (a)'s log, and their number per scenario is pinned below.
 // Prints "scenario <name>: calls <n>, failed <f>, discarded <d>" per scenario, then "ok" or the
-// failed checks.  Links every host source but hip_rt.cpp and mcs_runtime.cpp.
+// failed checks.  With the argument --args it prints (a) alone, every launch's argument block in
+// hex behind its line: the launch record two builds of libmcs are compared by.  Links every host
+// source but hip_rt.cpp and mcs_runtime.cpp.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +31,7 @@
 #include <vector>
 
 #include "mcs.h"
+#include "mcs_fparams.h"
 #include "stub_hip.h"
 
 static int g_bad = 0;
@@ -37,6 +47,9 @@ static hipStream_t g_stream = nullptr;     // the caller's stream of the overlap
 static int g_armed_calls = 0;              // runtime calls of a run up to its disarm()
 static int g_hook_cams = 0;                // copy hook: cameras of the plan at work
 static size_t g_hook_cover_bytes = 0;      // copy hook: size of the seam grid's cover copy
+static size_t g_hook_orb_bytes = 0;        // copy hook: size of the ORB copy back to "overflow"
+static size_t g_hook_scores_bytes = 0;     // copy hook: size of the RANSAC scores' copy
+static bool g_print_args = false;          // --args
 
 // Ends the part of a run that failures are injected into (what follows releases the plans).
 static void disarm()
@@ -58,6 +71,13 @@ static void copy_hook(void *dst, size_t bytes, hipStream_t)
         uint16_t *cov = (uint16_t *)dst;
         for (size_t i = 0; i < bytes / 2; i++) cov[i] = 3;
     }
+    if (g_hook_orb_bytes && bytes == g_hook_orb_bytes) {
+        // orb_detect's copy back, [counts .. sel]: one candidate on level 0, the overflow flag set
+        int *blob = (int *)dst;
+        blob[0] = 1;
+        blob[(bytes - 256) / sizeof(int) + 1] = 1;
+    }
+    if (g_hook_scores_bytes && bytes == g_hook_scores_bytes) ((int32_t *)dst)[3] = 5;
 }
 
 struct Plans {
@@ -190,23 +210,123 @@ static int run_match()
         if (rc == MCS_OK)
             rc = mcs_match_hamming_knn2_host(qb.data(), nq, tb.data(), nt, idx.data(), di.data(), 0);
     }
+    // RANSAC: no hypothesis scores 4 (the stub's zeros), then hypothesis 3 scores 5 (mask and model
+    // are fetched; the refinement of the all-zero model on no inliers is host arithmetic)
+    for (int i = 0; i < 2 && rc == MCS_OK; i++) {
+        const int n = 8, iters = 16;
+        float src[2 * n], dst[2 * n];
+        for (int q = 0; q < 2 * n; q++) src[q] = (float)(7 * q % 13), dst[q] = src[q] + 1.f;
+        double H[9];
+        uint8_t mask[n];
+        int ninl = -1;
+        g_hook_scores_bytes = i ? iters * sizeof(int32_t) : 0;
+        rc = mcs_ransac_homography_host(src, dst, n, 3.0, iters, 0, H, mask, &ninl, 0);
+        if (rc == MCS_OK) CHECK(ninl == (i ? 5 : 0));
+    }
+    g_hook_scores_bytes = 0;
     disarm();
     return rc;
 }
 
+static int run_orb()
+{
+    const int w = 64, h = 48, cap = 100;
+    float xy[2 * cap], resp[cap], ang[cap];
+    int lvl[cap], n = -1;
+    uint8_t desc[32 * cap];
+    // a host BGR frame, 3 levels at 1.2: the one-launch pyramid
+    int rc = mcs_orb_detect_host(g_frame.data(), w, h, 3, cap, 3, 1.2f, 20, xy, resp, ang, lvl,
+                                 desc, &n, 0);
+    // a device gray frame, 3 levels at 2.0: the per-level resize chain
+    if (rc == MCS_OK)
+        rc = mcs_orb_detect_device(DEV_CAMS[0], w, h, 1, cap, 3, 2.0f, 20, xy, resp, ang, lvl,
+                                   desc, &n, 0);
+    // one level: no pyramid
+    if (rc == MCS_OK)
+        rc = mcs_orb_detect_device(DEV_CAMS[1], w, h, 3, cap, 1, 1.2f, 20, xy, resp, ang, lvl,
+                                   desc, &n, 0);
+    if (rc == MCS_OK) CHECK(n == 0);
+    // 8 keypoints asked for, and a copy back that reports an overflowed ranking (copy_hook): the
+    // host ranks the one candidate and mcs_orb_describe runs again without the device's count.
+    // The copy back: counts, keypoints, descriptors, orientations, responses, [n, overflow],
+    // each rounded up to 256 bytes.
+    if (rc == MCS_OK) {
+        const auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        g_hook_orb_bytes = up(12 * 4) + up(8 * 12) + up(8 * 32) + up(8 * 16) + up(8 * 8) + up(8);
+        rc = mcs_orb_detect_host(g_frame.data(), w, h, 3, 8, 3, 1.2f, 20, xy, resp, ang, lvl, desc,
+                                 &n, 0);
+        g_hook_orb_bytes = 0;
+        if (rc == MCS_OK) {
+            CHECK(n == 1 && lvl[0] == 0);
+            mcs::KOrbDescArgs da;
+            bool seen = false;
+            for (const stub::Event &e : stub::g.log)
+                if (e.name == "mcs_orb_describe" && e.args_as(&da) && !da.sel)
+                    seen = e.gx == 1 && da.n == 1;
+            CHECK(seen);
+        }
+    }
+    disarm();
+    return rc;
+}
+
+static int rig_capture(mcs_rig_job *j, const uint8_t *const *frames)
+{
+    double H[9 * MCS_MAX_CAMS];
+    int ok[MCS_MAX_CAMS], nk[MCS_MAX_CAMS], nm[MCS_MAX_CAMS], ni[MCS_MAX_CAMS];
+    const int rc = mcs_rig_job_submit(j, frames, nullptr);
+    // (the worker thread makes the capture's runtime calls while this thread waits here: their
+    // order, and so the injection's count, is that of one thread)
+    return rc ? rc : mcs_rig_job_wait(j, H, ok, nk, nm, ni);
+}
+
+static int run_rig()
+{
+    const uint8_t *six[6];
+    for (int c = 0; c < 6; c++) six[c] = DEV_CAMS[c % 3] + 0x100000 * (c / 3);
+    mcs_rig_job *a = nullptr, *b = nullptr;
+    int rc = mcs_rig_job_create(3, 64, 48, 3, 100, 3, 1.2f, 20, 0.75f, 3.0, 64, 0, 0, &a);
+    if (rc == MCS_OK)   // 2 captures of 3 gray cameras, 2x levels: no one-launch pyramid, no graph
+        rc = mcs_rig_job_create_batch(3, 2, 64, 48, 1, 100, 3, 2.0f, 20, 0.75f, 3.0, 64, 0, 0, &b);
+    // the graph's capture, then its replay; a lens: the graph is dropped and captured again
+    for (int i = 0; i < 2 && rc == MCS_OK; i++) rc = rig_capture(a, DEV_CAMS);
+    const double K[9] = {60, 0, 32, 0, 60, 24, 0, 0, 1}, dist[4] = {0.01, 0, 0, 0};
+    if (rc == MCS_OK) rc = mcs_rig_job_set_lens(a, 1, K, dist, 4);
+    if (rc == MCS_OK) rc = rig_capture(a, DEV_CAMS);
+    if (rc == MCS_OK) rc = rig_capture(b, six);
+    if (rc == MCS_OK) {
+        // every capture stayed on the device path (the stub's copy back reports no overflow)
+        int dev = -1, calls = -1;
+        CHECK(mcs_rig_job_counts(a, &dev, &calls) == MCS_OK && dev == 3 && calls == 0);
+        CHECK(mcs_rig_job_counts(b, &dev, &calls) == MCS_OK && dev == 1 && calls == 0);
+        int graphs = 0, plain = 0;
+        for (const stub::Event &e : stub::g.log) {
+            graphs += e.name == "mcs_orb_pyramid" && e.gy == 3 && e.lds > 0;
+            plain += e.name == "mcs_resize_c1" && e.gz == 6;
+        }
+        CHECK(graphs == 2 && plain == 2);   // two captures of the graph; levels 1 and 2 resized
+    }
+    disarm();
+    CHECK(mcs_rig_job_destroy(a) == MCS_OK);
+    CHECK(mcs_rig_job_destroy(b) == MCS_OK);
+    return rc;
+}
+
 struct Snapshot {
-    size_t live, pinned, streams, events;
+    size_t live, pinned, streams, events, graphs, execs;
     int bad_free;
     bool operator==(const Snapshot &o) const
     {
         return live == o.live && pinned == o.pinned && streams == o.streams &&
-               events == o.events && bad_free == o.bad_free;
+               events == o.events && graphs == o.graphs && execs == o.execs &&
+               bad_free == o.bad_free;
     }
 };
 static Snapshot snapshot()
 {
     const stub::State &g = stub::g;
-    return {g.live.size(), g.pinned.size(), g.streams.size(), g.events.size(), g.bad_free};
+    return {g.live.size(),   g.pinned.size(), g.streams.size(), g.events.size(),
+            g.graphs.size(), g.execs.size(),  g.bad_free};
 }
 
 // One run with call k failing (0: none); the log is that run's alone.
@@ -237,7 +357,15 @@ static void scenario(const char *name, int (*run)(), int want_discarded)
         if (e.call >= 1 && e.call <= calls) kind[e.call] = e.kind, line[e.call] = (int)i;
     }
     printf("== %s: %d runtime calls, %zu events\n", name, calls, clean.size());
-    for (const std::string &l : clean) printf("%s\n", l.c_str());
+    for (size_t i = 0; i < clean.size(); i++) {
+        printf("%s", clean[i].c_str());
+        if (g_print_args && !stub::g.log[i].args.empty()) {
+            printf(" : ");
+            for (const uint8_t byte : stub::g.log[i].args) printf("%02x", byte);
+        }
+        printf("\n");
+    }
+    if (g_print_args) return;
     // (b)
     int failed = 0, discarded = 0;
     for (int k = 1; k <= calls; k++) {
@@ -267,8 +395,9 @@ static void scenario(const char *name, int (*run)(), int want_discarded)
     CHECK(discarded == want_discarded);
 }
 
-int main()
+int main(int argc, char **argv)
 {
+    g_print_args = argc > 1 && !strcmp(argv[1], "--args");
     CHECK(stub::hipStreamCreateWithFlags(&g_stream, 0) == hipSuccess);
     stub::g.copy_hook = copy_hook;
     // mcs_plan_find_seams begins with release_tables, which drains the plan's stream once the
@@ -278,6 +407,9 @@ int main()
     scenario("graphcut", run_graphcut, 0);
     scenario("overlap", run_overlap, 0);
     scenario("match", run_match, 0);
+    scenario("orb", run_orb, 0);
+    // (the jobs are released after the injected part, as the plans are)
+    scenario("rig", run_rig, 0);
     if (g_bad == 0) printf("ok\n");
     return g_bad ? 1 : 0;
 }

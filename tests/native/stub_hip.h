@@ -3,8 +3,9 @@
 // a program.  It provides
 //   - device memory as fake pointers (never dereferenced) kept in a live set, with double and
 //     unknown frees counted; pinned memory as real zeroed host memory (host code reads it);
-//   - streams and events as fake handles, counted;
-//   - a log, in order, of every launch (kernel name, grid, block, stream, argument block),
+//   - streams, events, graphs and executable graphs as fake handles, counted;
+//   - a log, in order, of every launch (kernel name, grid, block, LDS bytes, stream, argument
+//     block),
 //     synchronise, memset and copy, under a mutex (the rig job runs a worker thread);
 //   - a hook that fills a device-to-host copy;
 //   - failure injection: the k-th runtime call fails (or the k-th hipMalloc alone).  Every call
@@ -34,6 +35,7 @@ struct Event {
     char kind = 0;                 // 'L'aunch, 'S'ynchronise, 'M'emset, 'C'opy
     std::string name;              // launches: the kernel
     unsigned gx = 0, gy = 0, gz = 0, bx = 0, by = 0, bz = 0;
+    unsigned lds = 0;              // launches: dynamic LDS bytes
     hipStream_t stream = nullptr;
     size_t bytes = 0;              // memsets and copies: their size; launches: the argument block's
     void *dst = nullptr;
@@ -55,7 +57,7 @@ struct State {
     std::map<void *, size_t> live;     // device allocations and their sizes
     std::map<void *, size_t> pinned;   // pinned host allocations
     std::vector<void *> freed;         // what hipFree was given, in order
-    std::set<uintptr_t> streams, events;
+    std::set<uintptr_t> streams, events, graphs, execs;
     int mallocs = 0;                   // hipMalloc calls
     int bad_free = 0;                  // frees / destroys of something unknown or already freed
     int releases = 0;                  // hipFree / hipHostFree calls
@@ -88,6 +90,7 @@ inline void reset(int k = 0, bool mallocs_only = false)
     std::lock_guard<std::mutex> lk(g.mu);
     for (auto &p : g.pinned) free(p.first);
     g.live.clear(), g.pinned.clear(), g.freed.clear(), g.streams.clear(), g.events.clear();
+    g.graphs.clear(), g.execs.clear();
     g.log.clear();
     g.bad_free = g.releases = 0;
 }
@@ -288,6 +291,7 @@ inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t *gr)
 {
     STUB_CALL();
     *gr = (hipGraph_t)fresh();
+    g.graphs.insert((uintptr_t)*gr);
     return hipSuccess;
 }
 inline hipError_t hipGraphInstantiate(hipGraphExec_t *x, hipGraph_t, hipGraphNode_t *, char *,
@@ -295,11 +299,22 @@ inline hipError_t hipGraphInstantiate(hipGraphExec_t *x, hipGraph_t, hipGraphNod
 {
     STUB_CALL();
     *x = (hipGraphExec_t)fresh();
+    g.execs.insert((uintptr_t)*x);
     return hipSuccess;
 }
 STUB_OK(hipGraphLaunch, (hipGraphExec_t, hipStream_t))
-inline hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
-inline hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
+inline hipError_t hipGraphExecDestroy(hipGraphExec_t x)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!g.execs.erase((uintptr_t)x)) g.bad_free++;
+    return hipSuccess;
+}
+inline hipError_t hipGraphDestroy(hipGraph_t gr)
+{
+    std::lock_guard<std::mutex> lk(g.mu);
+    if (!g.graphs.erase((uintptr_t)gr)) g.bad_free++;
+    return hipSuccess;
+}
 inline hipError_t hipModuleGetFunction(hipFunction_t *f, hipModule_t, const char *)
 {
     STUB_CALL();
@@ -307,7 +322,7 @@ inline hipError_t hipModuleGetFunction(hipFunction_t *f, hipModule_t, const char
     return hipSuccess;
 }
 inline hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned gy, unsigned gz,
-                                        unsigned bx, unsigned by, unsigned bz, unsigned,
+                                        unsigned bx, unsigned by, unsigned bz, unsigned lds,
                                         hipStream_t s, void **, void **cfg)
 {
     STUB_CALL();
@@ -315,7 +330,7 @@ inline hipError_t hipModuleLaunchKernel(hipFunction_t f, unsigned gx, unsigned g
     e.kind = 'L';
     const auto it = g.names.find((uintptr_t)f);
     if (it != g.names.end()) e.name = it->second;
-    e.gx = gx, e.gy = gy, e.gz = gz, e.bx = bx, e.by = by, e.bz = bz;
+    e.gx = gx, e.gy = gy, e.gz = gz, e.bx = bx, e.by = by, e.bz = bz, e.lds = lds;
     e.stream = s;
     if (cfg) {   // {BUFFER_POINTER, args, BUFFER_SIZE, &size, END}
         e.bytes = *(const size_t *)cfg[3];
@@ -354,8 +369,9 @@ inline std::vector<std::string> log_lines()
     for (const Event &e : g.log) {
         char b[256];
         if (e.kind == 'L')
-            snprintf(b, sizeof(b), "L %s grid %ux%ux%u block %ux%ux%u args %zu stream s%d",
-                     e.name.c_str(), e.gx, e.gy, e.gz, e.bx, e.by, e.bz, e.bytes, id(e.stream));
+            snprintf(b, sizeof(b), "L %s grid %ux%ux%u block %ux%ux%u lds %u args %zu stream s%d",
+                     e.name.c_str(), e.gx, e.gy, e.gz, e.bx, e.by, e.bz, e.lds, e.bytes,
+                     id(e.stream));
         else if (e.kind == 'S')
             snprintf(b, sizeof(b), "S stream s%d", id(e.stream));
         else

@@ -113,6 +113,20 @@ def test_small_rig_pairs(w, h, seed, nfeatures):
         assert n == 9 and score == 4 and tied > 100 and in_wave >= 6, got
 
 
+def test_chain_rig_pairs():
+    """The resize-chain rig (feature_edges.RIG_CHAIN): every level step is 2x, every camera has
+    keypoints on two levels and both pairs have 5 matches, one more than RANSAC refuses."""
+    from multicamera_stitching_amd import rig
+    w, h, seed, nfeatures = fe.RIG_CHAIN
+    sizes = fe.level_sizes(w, h, 3, 2.0)
+    assert all(2 * a[0] <= b[0] for a, b in zip(sizes[1:], sizes)), sizes
+    _, frames, _ = rig.estimation_rig(3, w, h, 3, seed=seed)
+    levels = []
+    kps, pairs = fe.oracle_pairs(frames, nfeatures, 3, scale_factor=2.0, levels=levels)
+    assert kps == fe.RIG_CHAIN_KEYPOINTS and min(levels) >= 2, (kps, levels)
+    assert [len(s) for s, _ in pairs] == fe.RIG_CHAIN_MATCHES and min(fe.RIG_CHAIN_MATCHES) > 4
+
+
 def test_hamming_train_limit_is_an_argument_check():
     """2^23 train descriptors do not fit the key's 23 index bits: refused before anything touches
     the device (the same check the native program makes on mcs_match_hamming_knn2_host)."""

@@ -313,3 +313,26 @@ def test_rig_job_small_rigs(w, h, seed, nfeatures):
             assert np.array_equal(py[k], Hw)
     if (w, h, seed, nfeatures) in fe.RIG_TIED:
         assert py[0] is not None and stats["inliers"][0] == 4
+
+
+def test_rig_job_resize_chain():
+    """A three-camera job whose levels step by 2.0 (feature_edges.RIG_CHAIN): the one-launch
+    pyramid declines, so the job issues the per-level resize with a frame stride over the cameras
+    and plain launches instead of its graph.  The job equals the per-call steps (asserted with
+    counts() == (1, 0) in _job_equals_calls), and both the oracle's keypoint and match counts and
+    its RANSAC."""
+    from multicamera_stitching_amd import rig
+    w, h, seed, nfeatures = fe.RIG_CHAIN
+    _, frames, _ = rig.estimation_rig(3, w, h, 3, seed=seed)
+    kps, pairs = fe.oracle_pairs(frames, nfeatures, 3, scale_factor=2.0)
+    py, stats = _job_equals_calls(frames, w, h, 3, nlevels=3, scale_factor=2.0,
+                                  nfeatures=nfeatures)
+    print(w, h, seed, nfeatures, stats)
+    assert stats["keypoints"] == kps == fe.RIG_CHAIN_KEYPOINTS
+    assert stats["matches"] == [len(s) for s, _ in pairs] == fe.RIG_CHAIN_MATCHES
+    for k, (src, dst) in enumerate(pairs):
+        Hw, maskw, _, _ = oracle.ransac_homography(src, dst, 3.0, iters=2000, seed=0)
+        assert (py[k] is None) == (Hw is None)
+        assert stats["inliers"][k] == int(maskw.sum())
+        if Hw is not None:
+            assert np.array_equal(py[k], Hw)
