@@ -122,7 +122,6 @@ int mcs::feat::feature_kernels(const Api *A, int device, const FeatureKernels **
                    {"mcs_rig_ransac", &k.rig_ransac}, {"mcs_rig_best", &k.rig_best},
                    {"mcs_rig_hyp", &k.rig_hyp},       {"mcs_rig_unlens", &k.rig_unlens},
                    {"mcs_seam_flow_init", &k.seam_init}, {"mcs_seam_flow_hinit", &k.seam_hinit},
-                   {"mcs_seam_flow_relabel", &k.seam_relabel},
                    {"mcs_seam_flow_push", &k.seam_push},
                    {"mcs_seam_flow_active", &k.seam_active},
                    {"mcs_seam_flow_label", &k.seam_label},

@@ -1173,40 +1173,12 @@ extern "C" __global__ __launch_bounds__(256) void mcs_seam_flow_hinit(const mcs:
     a.h[q] = a.in[q] && a.snk[q] > 0 ? 1 : kSeamHInf;
 }
 
-// Global relabel: `iters` rounds of h(u) = 1 + min h(v) over residual arcs u -> v (atomicMin:
-// heights only fall), flag[0] set on any change.  A launch without a change is the fixpoint:
-// the exact residual distances to the sink.
-extern "C" __global__ __launch_bounds__(256) void mcs_seam_flow_relabel(const mcs::KSeamFlowArgs a)
-{
-    using namespace mcs;
-    int X, Y;
-    int64_t q;
-    const bool live = seam_box_point(a, X, Y, q) && a.in[q];
-    bool changed = false;
-    for (int it = 0; it < a.iters; it++) {
-        if (live) {
-            int32_t hm = kSeamHInf;
-#pragma unroll
-            for (int d = 0; d < 4; d++) {
-                if (seam_ld(&a.cap[d * a.np + q]) <= 0) continue;
-                const int64_t r = seam_nb(a, X, Y, q, d);
-                hm = min(hm, seam_ld(&a.h[r]));
-            }
-            if (hm < kSeamHInf && hm + 1 < seam_ld(&a.h[q])) {
-                atomicMin(&a.h[q], hm + 1);
-                changed = true;
-            }
-        }
-        __syncthreads();
-    }
-    if (changed) atomicOr(&a.flag[0], 1);
-}
-
-// Global relabel, tiled: the block's 16 x 16 heights and their one-point ring staged in LDS,
-// `iters` relaxation rounds there (LDS latency per round instead of an L2 round trip; the ring
-// is the value other blocks had at the launch's start), then every lowered height written back
-// with atomicMin and flag[0] set.  Launched until a launch changes nothing: the same fixpoint
-// (exact residual distances to the sink) as mcs_seam_flow_relabel.
+// Global relabel, tiled: rounds of h(u) = 1 + min h(v) over residual arcs u -> v (heights only
+// fall).  The block's 16 x 16 heights and their one-point ring are staged in LDS, `iters`
+// relaxation rounds run there (LDS latency per round instead of an L2 round trip; the ring is
+// the value other blocks had at the launch's start), then every lowered height is written back
+// with atomicMin and flag[0] set.  A launch without a change is the fixpoint: the exact residual
+// distances to the sink.
 extern "C" __global__ __launch_bounds__(256) void mcs_seam_flow_relabel_lds(
     const mcs::KSeamFlowArgs a)
 {

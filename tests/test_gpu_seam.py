@@ -1,11 +1,13 @@
 """GPU graph-cut seams (mcs_plan_find_seams): device sampling of the seam
-grid + device push-relabel max-flow (the host Dinic, MCS_SEAM_FLOW=host, is its checker), then
-the seam-labelled owner rule inside the stitch kernels, against the CPU restatement
-(oracle/orc_seam.c + orc_blend.c).  Bit-exact labels and panoramas."""
+grid + device push-relabel max-flow, then the seam-labelled owner rule inside the stitch kernels,
+against the CPU restatement (oracle/orc_seam.c + orc_blend.c): the oracle is the reference, the
+host Dinic (MCS_SEAM_FLOW=host) the second opinion.  Bit-exact labels and panoramas.  The inputs
+here are regular (full-height bands, 3 channels); test_gpu_seam_edges.py holds the irregular ones."""
 import numpy as np
 import pytest
 
 from oracle import oracle
+from seam_edges import synthetic_seam_grid as _synthetic_seam_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -77,27 +79,6 @@ def test_cylinder_c4_full_size_graphcut(mb_path):
     want, lab = ref(frames, 2, 2)
     assert np.array_equal(plan.seam_labels(), lab)
     assert _diff(plan.stitch_host(frames).reshape(want.shape), want) == 0
-
-
-def _synthetic_seam_grid(gw, gh, n, seed, noise):
-    """A cylinder-like grid: n cameras, each covering its column band plus overlaps, owner = the
-    nearest band centre; samples = one world + per-camera noise (noise 0: flat costs)."""
-    rng = np.random.default_rng(seed)
-    cols = np.arange(gw)
-    per = gw / n
-    ov = max(2, int(per * 0.4))
-    cov = np.zeros((gh, gw), np.uint16)
-    dist = []
-    for i in range(n):
-        c = i * per + per / 2
-        d = (cols - c + gw / 2) % gw - gw / 2
-        cov[:, np.abs(d) <= per / 2 + ov] |= np.uint16(1 << i)
-        dist.append(np.abs(d))
-    lab = np.repeat(np.argmin(np.stack(dist), 0).astype(np.uint8)[None, :], gh, 0)
-    world = rng.integers(0, 256, (gh, gw, 3), dtype=np.int32)
-    smp = np.stack([np.clip(world + rng.integers(-noise, noise + 1, world.shape), 0, 255)
-                    .astype(np.uint8) for _ in range(n)])
-    return lab, cov, smp
 
 
 @pytest.mark.parametrize("gw,gh,n,seed,noise", [(96, 40, 4, 0, 30), (160, 64, 6, 1, 60),
