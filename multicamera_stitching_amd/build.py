@@ -34,6 +34,7 @@ HOST_SRC = ["mcs_plan.cpp", "hip_rt.cpp", "mcs_runtime.cpp", "mcs_capi.cpp", "mc
             "mcs_seam.cpp", "mcs_refine.cpp", "mcs_group.cpp", "mcs_rig.cpp", "mcs_chain.cpp",
             "mcs_gain.cpp"]
 HEADERS = ["mcs_kparams.h", "mcs_dev.h", "mcs_fparams.h", "mcs_common.h", "hip_rt.h", "mcs_blend.h",
+           "mcs_mb_prep.h", "mcs_mb_levels.h", "mcs_mb_bands.h", "mcs_mb_blend.h",
            "mcs_gain.h", "mcs_ransac_core.h",
            "mcs_orb_core.h", "mcs_orb_pattern.h", "mcs_feat_int.h", "mcs_lens_core.h",
            "mcs_plan_state.h", "mcs_scratch.h"]

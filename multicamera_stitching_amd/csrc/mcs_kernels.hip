@@ -17,6 +17,10 @@
 #include "mcs_dev.h"
 
 #include "mcs_blend.h"
+#include "mcs_mb_prep.h"
+#include "mcs_mb_levels.h"
+#include "mcs_mb_bands.h"
+#include "mcs_mb_blend.h"
 #include "mcs_gain.h"
 
 namespace mcs {

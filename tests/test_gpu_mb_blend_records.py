@@ -161,3 +161,37 @@ def test_records_several_captures_per_launch(F):
     for f in range(F):
         want = oracle.blend_stitch(plan.describe(), shots[f], MULTIBAND)
         assert _diff(got[f].reshape(want.shape), want) == 0, f
+
+
+@pytest.mark.parametrize("ch", [1, 2, 4])
+def test_band_pass_other_channel_counts(ch):
+    """The band pass at 1, 2 and 4 channels (every other case with those channel counts has a
+    mosaic under 128 px a side and takes mcs_mb_levels).  The plan's own aligned launch first;
+    then one launch of F = 3 captures (an odd tail for the band pass's pairs of captures) whose
+    camera pointers start one byte off a 4-byte boundary, so the band pass takes its unaligned
+    window form -- every capture against the restatement."""
+    import torch
+    plan, cams = _world_plan(3, 160, 140, ch, seed=12)
+    st = _check_host(plan, cams)
+    assert st["mb_bands"] > 0, st
+    print("mb_bands", st["mb_bands"], "mb_bands_lds", st["mb_bands_lds"])
+    F, shift = 3, 1
+    rng = np.random.default_rng(7)
+    shots = [cams] + [[rng.integers(1, 256, size=c.shape, dtype=np.uint8) for c in cams]
+                      for _ in range(F - 1)]
+    fb = cams[0].size
+    dev = []
+    for i in range(len(cams)):
+        buf = torch.zeros(shift + F * fb + 16, dtype=torch.uint8)
+        for f in range(F):
+            buf[shift + f * fb: shift + (f + 1) * fb] = torch.from_numpy(shots[f][i].reshape(-1))
+        dev.append(buf.cuda())
+    pitch = (plan.out_w * ch + 63) // 64 * 64
+    out = torch.zeros((F, plan.out_h, pitch), dtype=torch.uint8, device="cuda")
+    plan.stitch_device([d.data_ptr() + shift for d in dev], [fb] * len(dev),
+                       out.data_ptr(), pitch, out[0].numel(), F, 0)
+    torch.cuda.synchronize()
+    got = out[:, :, :plan.out_w * ch].cpu().numpy()
+    for f in range(F):
+        want = oracle.blend_stitch(plan.describe(), shots[f], MULTIBAND)
+        assert _diff(got[f].reshape(want.shape), want) == 0, f
