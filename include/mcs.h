@@ -276,7 +276,8 @@ int mcs_stitch_device(mcs_plan *plan, const uint8_t *const *d_cams,
  * cylindrical; the same pixels as mcs_stitch_device, lensed plans (mcs_plan_set_lens) and seam
  * hints (mcs_plan_find_seams) included.  FEATHER is one pass over the mosaic (every slot's map,
  * sum d I / sum d per pixel: no owner pass, no tile lists, any number of contributors per
- * pixel).  MCS_BLEND_MULTIBAND: MCS_E_UNSUPPORTED (mcs_stitch_device).  Replaces, per capture,
+ * pixel).  MCS_BLEND_MULTIBAND: MCS_E_UNSUPPORTED (mcs_stitch_device, or without tables
+ * mcs_stitch_direct_multiband below, which takes a work area).  Replaces, per capture,
  * StitcherBase.calibrate (:258-354) followed by StitcherBase.stitch (:211-256). */
 int mcs_stitch_direct(mcs_plan *plan, const uint8_t *const *d_cams,
                       const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
@@ -368,6 +369,35 @@ int mcs_stitch_device_gained(mcs_plan *plan, const uint8_t *const *d_cams,
 int mcs_stitch_direct_gained(mcs_plan *plan, const uint8_t *const *d_cams,
                              const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
                              int64_t out_frame_stride, int n_frames, void *stream);
+/* The multi-band blend (MCS_BLEND_MULTIBAND: the 3-level blend of mcs_stitch_device, dense-seam
+ * rule included) without prepared tables, for a plan that lives for one capture: the same pixels
+ * as mcs_plan_prepare + mcs_stitch_device of the plan, bit for bit -- chain or cylindrical plans,
+ * lenses, seam hints, 1-4 channels, both interpolations, batches.  Two launches per call
+ * (csrc/mcs_direct_mb.hip): every pixel from its owner plus the owners of every 16 x 16 cell of
+ * the mosaic, then one block per 32 x 64 blend tile that blends the tiles whose neighbourhood
+ * holds two or more owners.  Between the two launches lives a small device work area that the
+ * CALLER owns (a plan that lives for one capture must not allocate: freeing synchronises):
+ * mcs_direct_multiband_work_size gives its size, which depends on the mosaic's size only --
+ * 4 bytes per 16 x 16 cell, 4 * ceil(out_w / 16) * ceil(out_h / 16); 0 for an empty mosaic.  It
+ * need not be initialised, and the next call on the same stream may reuse it; calls in flight on
+ * different streams need different areas.  d_work NULL or work_bytes below that size:
+ * MCS_E_INVALID, with the needed size in the message.  The plan must be a MULTIBAND plan
+ * (mcs_plan_set_blend, or a cylindrical plan's default): any other mode is MCS_E_INVALID (those
+ * are mcs_stitch_direct's; so single-camera warp / undistort plans, which take no blend mode, are
+ * refused).  Otherwise arguments, checks and the gains rule as mcs_stitch_direct /
+ * mcs_stitch_direct_gained: n_frames == 0 or an empty mosaic returns MCS_OK at once; the ungained
+ * form on a plan with gains is MCS_E_UNSUPPORTED; the gained form with gains disabled or the
+ * identity launches the ungained kernels.  Camera frame strides that differ take one pair of
+ * launches per frame.  No limit on mosaic or frame size. */
+int mcs_direct_multiband_work_size(const mcs_plan *plan, int64_t *bytes);
+int mcs_stitch_direct_multiband(mcs_plan *plan, const uint8_t *const *d_cams,
+                                const int64_t *cam_frame_stride, uint8_t *d_out,
+                                int64_t out_pitch, int64_t out_frame_stride, int n_frames,
+                                void *d_work, int64_t work_bytes, void *stream);
+int mcs_stitch_direct_multiband_gained(mcs_plan *plan, const uint8_t *const *d_cams,
+                                       const int64_t *cam_frame_stride, uint8_t *d_out,
+                                       int64_t out_pitch, int64_t out_frame_stride, int n_frames,
+                                       void *d_work, int64_t work_bytes, void *stream);
 /* q[i] of every camera (256 when gains are disabled) and whether gains are enabled; either
  * pointer may be NULL. */
 int mcs_plan_gains(const mcs_plan *plan, uint16_t *q, int *enabled);
@@ -562,6 +592,13 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *job, double *H_io, int *ok_io, in
  * MCS_BLEND_SEAM or MCS_BLEND_FEATHER; any other mode: MCS_E_INVALID.  Holds until changed; call
  * it between captures, not while a wait_stitch of the job runs. */
 int mcs_rig_job_set_blend(mcs_rig_job *job, int mode);
+/* on != 0: the per-capture plan of mcs_rig_job_wait_stitch[_batch] is a MCS_BLEND_MULTIBAND plan
+ * rendered by mcs_stitch_direct_multiband (with exposure enabled: its _gained form; lenses as
+ * for every mode).  The mode given to mcs_rig_job_set_blend is kept and applies again after
+ * on = 0 (the default).  The job owns the work area and only grows it (allocated before the
+ * capture's launches, never freed between captures).  The calling rule of
+ * mcs_rig_job_set_blend. */
+int mcs_rig_job_set_multiband(mcs_rig_job *job, int on);
 /* Per-capture exposure gains of mcs_rig_job_wait_stitch[_batch] (see there): step_log2 0..4
  * enables them on that grid step, a negative step_log2 disables them (the default: the calls
  * launch exactly what they launch without this entry point); any other step: MCS_E_INVALID.

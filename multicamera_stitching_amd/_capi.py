@@ -57,6 +57,8 @@ EXPORTS = (
     "mcs_rig_job_set_blend", "mcs_plan_overlap_stats_direct",
     "mcs_plan_overlap_stats_direct_async", "mcs_rig_job_set_exposure", "mcs_rig_job_gains",
     "mcs_lens_unmap_host", "mcs_rig_job_set_lens",
+    "mcs_direct_multiband_work_size", "mcs_stitch_direct_multiband",
+    "mcs_stitch_direct_multiband_gained", "mcs_rig_job_set_multiband",
 )
 MCS_GROUP_ID_BYTES = 128
 
@@ -316,6 +318,16 @@ def load() -> ctypes.CDLL:
         L.mcs_stitch_device_gained.restype = I
         L.mcs_stitch_direct_gained.argtypes = L.mcs_stitch_device.argtypes
         L.mcs_stitch_direct_gained.restype = I
+        L.mcs_direct_multiband_work_size.argtypes = [P, ctypes.POINTER(ctypes.c_int64)]
+        L.mcs_direct_multiband_work_size.restype = I
+        L.mcs_stitch_direct_multiband.argtypes = [
+            P, ctypes.POINTER(P), ctypes.POINTER(ctypes.c_int64), P, ctypes.c_int64,
+            ctypes.c_int64, I, P, ctypes.c_int64, P]
+        L.mcs_stitch_direct_multiband.restype = I
+        L.mcs_stitch_direct_multiband_gained.argtypes = L.mcs_stitch_direct_multiband.argtypes
+        L.mcs_stitch_direct_multiband_gained.restype = I
+        L.mcs_rig_job_set_multiband.argtypes = [P, I]
+        L.mcs_rig_job_set_multiband.restype = I
         L.mcs_group_unique_id.argtypes = [P]
         L.mcs_group_unique_id.restype = I
         L.mcs_group_create.argtypes = [I, I, P, I, ctypes.POINTER(P)]
@@ -586,6 +598,41 @@ class Plan:
         check(self._lib.mcs_stitch_device_gained(
             self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
             int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(stream))))
+
+    def direct_multiband_work_size(self) -> int:
+        """mcs_direct_multiband_work_size: bytes of the device work area stitch_direct_multiband
+        needs for this plan's mosaic (4 per 16 x 16 cell)."""
+        n = ctypes.c_int64(0)
+        check(self._lib.mcs_direct_multiband_work_size(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def _stitch_direct_multiband(self, fn, cam_ptrs, cam_frame_strides, out_ptr, out_pitch,
+                                 out_frame_stride, n_frames, work_ptr, work_bytes, stream):
+        n = len(cam_ptrs)
+        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
+        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
+        check(fn(self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
+                 int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(work_ptr)),
+                 int(work_bytes), ctypes.c_void_p(int(stream))))
+
+    def stitch_direct_multiband(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
+                                out_frame_stride: int, n_frames: int, work_ptr: int,
+                                work_bytes: int, stream: int = 0):
+        """mcs_stitch_direct_multiband: the multi-band blend of a MULTIBAND plan without prepared
+        tables (the same pixels as prepare + stitch_device).  work_ptr / work_bytes: a device
+        work area of the caller of at least direct_multiband_work_size() bytes; it need not be
+        initialised and may be reused by the next call on the same stream."""
+        self._stitch_direct_multiband(self._lib.mcs_stitch_direct_multiband, cam_ptrs,
+                                      cam_frame_strides, out_ptr, out_pitch, out_frame_stride,
+                                      n_frames, work_ptr, work_bytes, stream)
+
+    def stitch_direct_multiband_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int,
+                                       out_pitch: int, out_frame_stride: int, n_frames: int,
+                                       work_ptr: int, work_bytes: int, stream: int = 0):
+        """mcs_stitch_direct_multiband_gained: the same with the plan's gains in the kernels."""
+        self._stitch_direct_multiband(self._lib.mcs_stitch_direct_multiband_gained, cam_ptrs,
+                                      cam_frame_strides, out_ptr, out_pitch, out_frame_stride,
+                                      n_frames, work_ptr, work_bytes, stream)
 
     def stitch_direct_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
                              out_frame_stride: int, n_frames: int, stream: int = 0):
@@ -1124,6 +1171,12 @@ class RigJob:
         """Blend mode of the capture's stitch in wait_stitch (mcs_rig_job_set_blend):
         MCS_BLEND_NONE (the default), MCS_BLEND_SEAM or MCS_BLEND_FEATHER."""
         check(self._lib.mcs_rig_job_set_blend(self._h, int(mode)))
+
+    def set_multiband(self, on: bool):
+        """mcs_rig_job_set_multiband: wait_stitch renders the capture's mosaic with the multi-band
+        blend (mcs_stitch_direct_multiband; the job owns the work area).  The mode given to
+        set_blend is kept and applies again after set_multiband(False)."""
+        check(self._lib.mcs_rig_job_set_multiband(self._h, 1 if on else 0))
 
     def set_exposure(self, step_log2: int, alpha: float = 0.0, beta: float = 0.0):
         """Per-capture exposure gains in wait_stitch (mcs_rig_job_set_exposure): statistics on

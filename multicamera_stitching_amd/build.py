@@ -2,7 +2,8 @@
 
 Two steps:
   1. hipcc compiles each device source device-only for gfx950 into a code object
-     (csrc/mcs_kernels.hip: the stitch path; csrc/mcs_features.hip: matching/estimation);
+     (csrc/mcs_kernels.hip: the stitch path; csrc/mcs_features.hip: matching/estimation;
+     csrc/mcs_sweep.hip: the multi-band sweep; csrc/mcs_direct_mb.hip: the direct multi-band);
   2. g++ compiles the host side (plan builder, HIP runtime binding, C ABI) and embeds those code
      objects (.incbin) into libmcs.so.  libmcs links no HIP runtime: it binds to the one the process
      already has (PyTorch's) or to ROCm's (csrc/hip_rt.h explains why).
@@ -24,7 +25,11 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmcs.so")
 ARCH = os.environ.get("MCS_OFFLOAD_ARCH", "gfx950")
 # device sources -> embedded code objects (blob symbol mcs_hsaco_<name>_start)
-DEVICE = {"stitch": "mcs_kernels.hip", "features": "mcs_features.hip", "sweep": "mcs_sweep.hip"}
+DEVICE = {"stitch": "mcs_kernels.hip", "features": "mcs_features.hip", "sweep": "mcs_sweep.hip",
+          "direct_mb": "mcs_direct_mb.hip"}
+# the code objects mcs_build_id names: the code bench.py times and the counter records attach to
+# (the direct multi-band object is loaded beside them and kept out of the id)
+ID_OBJECTS = ("features", "stitch", "sweep")
 HSACO = os.path.join(HERE, f"mcs_kernels.{ARCH}.hsaco")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))
@@ -137,7 +142,7 @@ def _build_to(LIB: str, HSACO: str, defines, verbose: bool) -> str:
                   os.path.join(CSRC, src)], verbose)
             os.replace(out + ".tmp", out)
         objs[name] = out
-    build_id = code_id([objs[name] for name in sorted(objs)])
+    build_id = code_id([objs[name] for name in ID_OBJECTS])
     blob = LIB + ".blob.S"
     with open(blob, "w") as f:
         f.write("    .section .rodata\n")

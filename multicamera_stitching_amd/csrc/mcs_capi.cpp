@@ -559,7 +559,106 @@ static int stitch_direct_launch(mcs_plan *p, const uint8_t *const *d_cams,
     return MCS_OK;
 }
 
+// mcs_stitch_direct_multiband(_gained) after the gains refusal: two launches per run of frames
+// (csrc/mcs_direct_mb.hip), the caller's work area between them.
+static int stitch_direct_mb_launch(mcs_plan *p, const uint8_t *const *d_cams,
+                                   const int64_t *cam_frame_stride, uint8_t *d_out,
+                                   int64_t out_pitch, int64_t out_frame_stride, int n_frames,
+                                   void *d_work, int64_t work_bytes, void *stream, bool gained)
+{
+    mcs::KParams kp;
+    int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                            n_frames, &kp);
+    if (rc) return rc;
+    if (p->blend != MCS_BLEND_MULTIBAND)
+        return mcs::fail(MCS_E_INVALID, "mcs_stitch_direct_multiband renders multi-band plans "
+                         "(mcs_plan_set_blend MCS_BLEND_MULTIBAND); paste / seam / feather plans "
+                         "are mcs_stitch_direct's");
+    if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames == 0) return MCS_OK;
+    const int64_t need = mcs::direct_mb_work_bytes(kp.out_w, kp.out_h);
+    if (!d_work || work_bytes < need)
+        return mcs::fail(MCS_E_INVALID, "mcs_stitch_direct_multiband: the work area (%s, %lld "
+                         "bytes) must hold %lld bytes (mcs_direct_multiband_work_size)",
+                         d_work ? "given" : "NULL", (long long)work_bytes, (long long)need);
+    gained = gained && gains_active(p);
+    if (gained) fill_gain_q(p, &kp);
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
+    const Kernels *k = nullptr;
+    rc = kernels(A, p->device, &k);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    rc = upload_plan_tables(A, p, s);   // (cylinder / lensed plans: their device tables, once)
+    if (rc) return rc;
+    kp.cyl_tab = p->kp.cyl_tab;
+    kp.map_tab = p->kp.map_tab;
+    kp.lens_tab = p->kp.lens_tab;
+    kp.seam_hint = p->kp.seam_hint;
+    kp.base = nullptr;   // (the kernels address frames by pointer)
+    const int C = p->fd.channels, I = p->fd.interp;
+    const int gx = (kp.out_w + mcs::kTileW - 1) / mcs::kTileW;
+    const int gy = (kp.out_h + mcs::kTileH - 1) / mcs::kTileH;
+    // one frame stride for every camera per launch, else frame by frame (as mcs_stitch_direct)
+    bool uniform = true;
+    for (int j = 0; j < p->fd.n_stages; j++)
+        uniform = uniform && kp.cam_fstride[p->fd.st[j].cam] == kp.cam_fstride[0];
+    const int runs = uniform ? 1 : n_frames;
+    for (int f = 0; f < runs; f++) {
+        mcs::KDirectMbArgs args;
+        args.P = kp;
+        if (!uniform) {
+            for (int i = 0; i < p->fd.n_cams; i++)
+                args.P.cams[i] = kp.cams[i] ? kp.cams[i] + (int64_t)f * kp.cam_fstride[i] : nullptr;
+            args.P.out = kp.out + (int64_t)f * kp.out_fstride;
+        }
+        args.cells = static_cast<uint32_t *>(d_work);
+        args.n_frames = uniform ? n_frames : 1;
+        args.gxb = (kp.out_w + mcs::kBlendTileW - 1) / mcs::kBlendTileW;
+        args.gyb = (kp.out_h + mcs::kBlendTileH - 1) / mcs::kBlendTileH;
+        args.cgx = mcs::dmb_cells(kp.out_w);
+        args.cgy = mcs::dmb_cells(kp.out_h);
+        args.pad_ = 0;
+        const unsigned fy = (unsigned)((args.n_frames + mcs::kDirectFrames - 1) / mcs::kDirectFrames);
+        rc = launch_args(A, k->direct_mb_own[gained][C][I], (unsigned)(gx * gy), fy, mcs::kWave,
+                         mcs::kWavesPerBlock, &args, sizeof(args), s);
+        if (rc) return rc;
+        rc = launch_args(A, k->direct_mb_tile[gained][C][I], (unsigned)(args.gxb * args.gyb),
+                         (unsigned)args.n_frames, mcs::kDmbTileThreads, 1, &args, sizeof(args), s, 1,
+                         (unsigned)mcs::dmb_lds(C).bytes);
+        if (rc) return rc;
+    }
+    return MCS_OK;
+}
+
 extern "C" {
+
+int mcs_direct_multiband_work_size(const mcs_plan *p, int64_t *bytes)
+{
+    mcs::clear_error();
+    if (!p || !bytes) return mcs::fail(MCS_E_INVALID, "NULL plan/bytes");
+    *bytes = mcs::direct_mb_work_bytes(p->fd.out_w, p->fd.out_h);
+    return MCS_OK;
+}
+
+int mcs_stitch_direct_multiband(mcs_plan *p, const uint8_t *const *d_cams,
+                                const int64_t *cam_frame_stride, uint8_t *d_out,
+                                int64_t out_pitch, int64_t out_frame_stride, int n_frames,
+                                void *d_work, int64_t work_bytes, void *stream)
+{
+    const int rc = refuse_gains(p, "mcs_stitch_direct_multiband");
+    if (rc) return rc;
+    return stitch_direct_mb_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                                   n_frames, d_work, work_bytes, stream, false);
+}
+
+int mcs_stitch_direct_multiband_gained(mcs_plan *p, const uint8_t *const *d_cams,
+                                       const int64_t *cam_frame_stride, uint8_t *d_out,
+                                       int64_t out_pitch, int64_t out_frame_stride, int n_frames,
+                                       void *d_work, int64_t work_bytes, void *stream)
+{
+    return stitch_direct_mb_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
+                                   n_frames, d_work, work_bytes, stream, true);
+}
 
 int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
                       uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,

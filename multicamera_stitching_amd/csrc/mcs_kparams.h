@@ -423,6 +423,56 @@ struct KMbSweepArgs {
 };
 
 constexpr int kDirectFrames = 4;    // captures per direct-gather block
+
+// Direct multi-band (mcs_direct_mb.hip, mcs_stitch_direct_multiband): the owner pass writes, per
+// kDmbCell x kDmbCell cell of the mosaic, the OR of its pixels' owner slot bits into the caller's
+// work area (one u32 per cell, row-major); the tile pass ORs the cells of a blend tile's grown
+// neighbourhood (the tile and its kBlendHalo are whole cells) to choose its rule.
+constexpr int kDmbCell = 16;
+static_assert(kTileH == kDmbCell && kTileW % kDmbCell == 0,
+              "every cell lies inside exactly one tile of the owner pass");
+static_assert(kBlendTileW % kDmbCell == 0 && kBlendTileH % kDmbCell == 0 && kBlendHalo == kDmbCell,
+              "a blend tile's grown neighbourhood is whole cells");
+constexpr int kDmbTileThreads = 512;
+constexpr int dmb_cells(int n) { return (n + kDmbCell - 1) / kDmbCell; }
+constexpr int64_t direct_mb_work_bytes(int out_w, int out_h)
+{
+    return out_w > 0 && out_h > 0 ? (int64_t)4 * dmb_cells(out_w) * dmb_cells(out_h) : 0;
+}
+struct KDirectMbArgs {
+    KParams P;
+    uint32_t *cells;               // the work area: [cgy][cgx] owner slot bits per cell
+    int n_frames;
+    int gxb, gyb;                  // blend-tile grid (tile pass)
+    int cgx, cgy;                  // cell grid
+    int pad_;
+};
+// Dynamic LDS of a tile-pass block (byte offsets), for `cn` channels: the int64 numerators of the
+// R1 region and of level 2 (then B2 / R1 as doubles in their place), one owner's level-0 samples
+// (packed bytes), g1, g2 (int32 per channel), m2, the denominators, L0 of the tile's pixels
+// (int32 per channel), m1 (u16) and the owner map of the used neighbourhood (local slot, u8).
+struct DmbLds {
+    int num1, num2, g0, g1, g2, m2, den1, den2, l0, m1, own, bytes;
+};
+constexpr DmbLds dmb_lds(int cn)
+{
+    DmbLds L{};
+    int at = 0;
+    L.num1 = at, at += kMbNRX * kMbNRY * cn * 8;
+    L.num2 = at, at += kMbN2X * kMbN2Y * cn * 8;
+    L.g0 = at, at += kMbUsedX * kMbUsedY * 4;
+    L.g1 = at, at += kMbN1X * kMbN1Y * cn * 4;
+    L.g2 = at, at += kMbN2X * kMbN2Y * cn * 4;
+    L.m2 = at, at += kMbN2X * kMbN2Y * 4;
+    L.den1 = at, at += kMbNRX * kMbNRY * 4;
+    L.den2 = at, at += kMbN2X * kMbN2Y * 4;
+    L.l0 = at, at += kMbTilePx * cn * 4;
+    L.m1 = at, at += (kMbN1X * kMbN1Y * 2 + 3) & ~3;
+    L.own = at, at += kMbUsedX * kMbUsedY;
+    L.bytes = (at + 15) & ~15;
+    return L;
+}
+static_assert(dmb_lds(4).bytes <= 160 * 1024, "tile pass: one block's LDS fits a CU");
 // Footprint rows per wave per capture (a tile needing more goes to the direct path).  8 x 8 = 64
 // rows covers every tile of the C4 cylinder rig, whose top and bottom tiles' footprints curve
 // over ~40 source rows per camera (6 per wave left 215 of its 3672 tiles on the direct path:

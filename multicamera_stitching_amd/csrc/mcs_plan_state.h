@@ -203,10 +203,14 @@ struct Kernels {
     hipFunction_t direct_feather_g[5][2] = {};
     // table-free overlap statistics (mcs_plan_overlap_stats_direct): [channels][interp]
     hipFunction_t direct_overlap[5][2] = {};
+    // direct multi-band (module kModDirectMb, mcs_stitch_direct_multiband): the owner pass and the
+    // tile pass, [gained][channels][interp]
+    hipFunction_t direct_mb_own[2][5][2] = {};
+    hipFunction_t direct_mb_tile[2][5][2] = {};
 };
 
 // mcs_prepare.cpp
-// The stitch and sweep modules' kernels on `device` (looked up once per device).
+// The stitch, sweep and direct multi-band modules' kernels on `device` (looked up once per device).
 int kernels(const Api *A, int device, const Kernels **out);
 // The plan-lifetime device tables (cylinder table, map, lens rows), uploaded when missing / stale.
 int upload_plan_tables(const Api *A, mcs_plan *p, hipStream_t s);

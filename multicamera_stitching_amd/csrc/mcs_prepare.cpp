@@ -123,6 +123,17 @@ int kernels(const Api *A, int device, const Kernels **out)
                 snprintf(name, sizeof(name), "mcs_direct_overlap_c%d_i%d", c, i);
                 rc = fn(name, &k.direct_overlap[c][i]);
             }
+        for (int g = 0; g < 2 && rc == MCS_OK; g++)
+            for (int c = 1; c <= 4 && rc == MCS_OK; c++)
+                for (int i = 0; i < 2 && rc == MCS_OK; i++) {
+                    snprintf(name, sizeof(name), "mcs_direct_mb_own_c%d_i%d%s", c, i, g ? "_g" : "");
+                    rc = mcs::module_function(A, device, mcs::kModDirectMb, name,
+                                              &k.direct_mb_own[g][c][i]);
+                    snprintf(name, sizeof(name), "mcs_direct_mb_tile_c%d_i%d%s", c, i, g ? "_g" : "");
+                    if (rc == MCS_OK)
+                        rc = mcs::module_function(A, device, mcs::kModDirectMb, name,
+                                                  &k.direct_mb_tile[g][c][i]);
+                }
         if (rc) return rc;
         k.loaded = true;
     }

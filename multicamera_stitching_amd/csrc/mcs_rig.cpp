@@ -150,6 +150,12 @@ struct mcs_rig_job {
     int captures_device = 0, captures_calls = 0;   // captures finished by each path
     // blend mode of the per-capture plan of wait_stitch (mcs_rig_job_set_blend)
     int blend = MCS_BLEND_NONE;
+    // mcs_rig_job_set_multiband: the per-capture plan is a MULTIBAND plan rendered by
+    // mcs_stitch_direct_multiband (blend above is kept for when it is switched off); the work area
+    // between that call's two launches, the job's, only ever grown
+    bool multiband = false;
+    void *d_mbwork = nullptr;
+    int64_t mbwork_bytes = 0;
     // per-capture exposure gains of wait_stitch (mcs_rig_job_set_exposure): the grid step (< 0:
     // off), the solver's constants, the last call's gains and their q (n_caps x n_cams), and the
     // statistics' buffers (n_caps x (N, S): device and pinned host; allocated on first use)
@@ -372,6 +378,24 @@ void device_release(mcs_rig_job *j)
     if (j->d_stats) (void)A->hipFree(j->d_stats);
     if (j->h_stats) (void)A->hipHostFree(j->h_stats);
     j->d_stats = j->h_stats = nullptr;
+    if (j->d_mbwork) (void)A->hipFree(j->d_mbwork);
+    j->d_mbwork = nullptr;
+    j->mbwork_bytes = 0;
+}
+
+// The job's direct multi-band work area, at least `bytes` (a mosaic larger than any before grows
+// it: the one time a capture's stitch allocates).
+int multiband_work(mcs_rig_job *j, int64_t bytes)
+{
+    if (j->d_mbwork && j->mbwork_bytes >= bytes) return MCS_OK;
+    const mcs::Entry A(j->device);
+    if (A.status) return A.status;
+    if (j->d_mbwork) (void)A->hipFree(j->d_mbwork);
+    j->d_mbwork = nullptr;
+    j->mbwork_bytes = 0;
+    HIP_TRY(A->hipMalloc(&j->d_mbwork, (size_t)(bytes > 0 ? bytes : 1)));
+    j->mbwork_bytes = bytes;
+    return MCS_OK;
 }
 
 // The statistics' buffers of a job with exposure enabled: n_caps x (N, S of one frame).
@@ -700,7 +724,8 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         for (int cam = 0; cam < N && r == MCS_OK; cam++)
             if ((j->lens_mask >> cam) & 1u)
                 r = mcs_plan_set_lens(plan, cam, j->lens_K[cam], j->lens_dist[cam], j->lens_nd[cam]);
-        if (r == MCS_OK && j->blend != MCS_BLEND_NONE) r = mcs_plan_set_blend(plan, j->blend);
+        const int blend = j->multiband ? (int)MCS_BLEND_MULTIBAND : j->blend;
+        if (r == MCS_OK && blend != MCS_BLEND_NONE) r = mcs_plan_set_blend(plan, blend);
         if (r == MCS_OK) r = mcs_plan_out_shape(plan, &w, &h, &c);
         if (r == MCS_OK && ((int64_t)w * c > out_pitch || (int64_t)h * out_pitch > out_capacity))
             r = mcs::fail(MCS_E_SHAPE, "mosaic %d x %d does not fit the output (pitch %lld, "
@@ -714,6 +739,21 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         *out = plan;
         return MCS_OK;
     };
+    // Capture q's stitch: mcs_stitch_direct[_gained], or with set_multiband its multi-band form
+    // with the job's work area (the captures of a call run on one stream and share it).
+    const auto stitch = [&](int q, mcs_plan *plan, bool gained) -> int {
+        const uint8_t *const *cams = j->frames.data() + (size_t)q * N;
+        const int64_t ofs = out_pitch * out_h[q];
+        if (!j->multiband)
+            return (gained ? mcs_stitch_direct_gained : mcs_stitch_direct)(
+                plan, cams, fs, d_out[q], out_pitch, ofs, 1, stream);
+        int64_t bytes = 0;
+        int r = mcs_direct_multiband_work_size(plan, &bytes);
+        if (r == MCS_OK) r = multiband_work(j, bytes);
+        if (r) return r;
+        return (gained ? mcs_stitch_direct_multiband_gained : mcs_stitch_direct_multiband)(
+            plan, cams, fs, d_out[q], out_pitch, ofs, 1, j->d_mbwork, j->mbwork_bytes, stream);
+    };
     if (j->exp_step < 0) {
         for (int q = 0; q < j->n_caps; q++) {
             mcs_plan *plan = nullptr;
@@ -721,8 +761,7 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
             if (rc) return rc;
             // (the plan's geometry travels in the kernel arguments: it may go right after the
             // launch)
-            rc = mcs_stitch_direct(plan, j->frames.data() + (size_t)q * N, fs, d_out[q], out_pitch,
-                                   out_pitch * out_h[q], 1, stream);
+            rc = stitch(q, plan, false);
             mcs_plan_destroy(plan);
             if (rc) return rc;
         }
@@ -759,9 +798,7 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         rc = mcs_gain_solve_host(N, st, st + (size_t)N * N, j->channels, j->exp_alpha, j->exp_beta, g);
         if (rc == MCS_OK) rc = mcs_plan_set_gains(plans[q], g);
         if (rc == MCS_OK) rc = mcs_plan_gains(plans[q], j->gain_q.data() + (size_t)q * N, nullptr);
-        if (rc == MCS_OK)
-            rc = mcs_stitch_direct_gained(plans[q], j->frames.data() + (size_t)q * N, fs, d_out[q],
-                                          out_pitch, out_pitch * out_h[q], 1, stream);
+        if (rc == MCS_OK) rc = stitch(q, plans[q], true);
     }
     for (mcs_plan *plan : plans) mcs_plan_destroy(plan);
     return rc;
@@ -788,6 +825,14 @@ int mcs_rig_job_set_blend(mcs_rig_job *j, int mode)
         return mcs::fail(MCS_E_INVALID, "blend mode %d: a rig job stitches with the direct path "
                          "(NONE, SEAM or FEATHER)", mode);
     j->blend = mode;
+    return MCS_OK;
+}
+
+int mcs_rig_job_set_multiband(mcs_rig_job *j, int on)
+{
+    mcs::clear_error();
+    if (!j) return mcs::fail(MCS_E_INVALID, "NULL job");
+    j->multiband = on != 0;
     return MCS_OK;
 }
 

@@ -7,6 +7,7 @@
 extern "C" const unsigned char mcs_hsaco_stitch_start[];
 extern "C" const unsigned char mcs_hsaco_features_start[];
 extern "C" const unsigned char mcs_hsaco_sweep_start[];
+extern "C" const unsigned char mcs_hsaco_direct_mb_start[];
 
 namespace mcs {
 
@@ -16,6 +17,7 @@ std::mutex g_mod_mu;
 
 const unsigned char *blob(Module m)
 {
+    if (m == kModDirectMb) return mcs_hsaco_direct_mb_start;
     return m == kModStitch ? mcs_hsaco_stitch_start
                            : (m == kModSweep ? mcs_hsaco_sweep_start : mcs_hsaco_features_start);
 }

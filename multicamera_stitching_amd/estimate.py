@@ -156,7 +156,7 @@ class CaptureEstimator:
                  iters: int = 2000, seed: int = 0, super_mode: bool = False,
                  interp: int = _capi.MCS_INTER_LINEAR, device: int = 0, threads: int = None,
                  captures_per_job: int = 1, blend: int = _capi.MCS_BLEND_NONE,
-                 exposure: int = None, lenses=None):
+                 exposure: int = None, lenses=None, multiband: bool = False):
         self.n_cams, self.w, self.h, self.c = n_cams, width, height, channels
         # per-capture exposure gains of collect_stitch (mcs_rig_job_set_exposure): the grid step
         # step_log2 (0..4) of the overlap statistics, or None for none; .gains: the last
@@ -171,6 +171,16 @@ class CaptureEstimator:
         if blend not in (_capi.MCS_BLEND_NONE, _capi.MCS_BLEND_SEAM, _capi.MCS_BLEND_FEATHER):
             raise ValueError(f"blend mode {blend}: the direct stitch renders NONE, SEAM or FEATHER")
         self.blend = blend
+        # multiband: stitch / collect_stitch render the multi-band blend instead
+        # (mcs_stitch_direct_multiband, mcs_rig_job_set_multiband).  It is no direct blend mode
+        # (it needs a work area between its two launches): its own switch, with blend left NONE.
+        # The rig jobs own their work areas; the Python-issued stitch() uses one torch buffer of
+        # the estimator, grown on demand (_mb_work).
+        if multiband and blend != _capi.MCS_BLEND_NONE:
+            raise ValueError(f"multiband=True with blend mode {blend}: one or the other")
+        self.multiband = bool(multiband)
+        self._mb_buf = None
+        self._mb_old = []
         # rig jobs of several captures (mcs_rig_job_create_batch: one launch chain over all their
         # cameras; submit / collect_stitch then take that many captures at once)
         self.batch = captures_per_job
@@ -193,6 +203,8 @@ class CaptureEstimator:
             if j is not None:
                 j.close()
         self._jobs = []
+        self._mb_buf = None
+        self._mb_old = []
         self.ahead.shutdown()
         self.fpool.shutdown()
         self.pool.shutdown()
@@ -228,6 +240,8 @@ class CaptureEstimator:
                                             self.device, captures=self.batch)
             if self.blend != _capi.MCS_BLEND_NONE:
                 self._jobs[slot].set_blend(self.blend)
+            if self.multiband:
+                self._jobs[slot].set_multiband(True)
             if self.exposure is not None:
                 self._jobs[slot].set_exposure(self.exposure)
             for cam, (K, dist) in sorted(self.lenses.items()):
@@ -375,12 +389,33 @@ class CaptureEstimator:
         """Stitch one capture with its homographies into out (rows out_pitch bytes apart,
         out_capacity bytes).  Returns the plan (its out_w / out_h give the mosaic's size)."""
         plan, _ = self.plan(pair_H)
-        if self.blend != _capi.MCS_BLEND_NONE:
+        if self.multiband:
+            plan.set_blend(_capi.MCS_BLEND_MULTIBAND)
+        elif self.blend != _capi.MCS_BLEND_NONE:
             plan.set_blend(self.blend)
         if plan.out_w * self.c > out_pitch or plan.out_h * out_pitch > out_capacity:
             plan.close()
             raise ValueError(f"mosaic {plan.out_w} x {plan.out_h} does not fit the output buffer")
         fs = self.w * self.h * self.c
+        if self.multiband:
+            work = self._mb_work(plan.direct_multiband_work_size())
+            plan.stitch_direct_multiband(frame_ptrs, [fs] * self.n_cams, out_ptr, out_pitch,
+                                         out_pitch * plan.out_h, 1, work.data_ptr(),
+                                         work.numel(), stream)
+            return plan
         plan.stitch_direct(frame_ptrs, [fs] * self.n_cams, out_ptr, out_pitch,
                            out_pitch * plan.out_h, 1, stream)
         return plan
+
+    def _mb_work(self, nbytes: int):
+        """The estimator's work area of the Python-issued multi-band stitch: one torch buffer on
+        the estimator's device, replaced by a larger one when a mosaic needs it (a replaced buffer
+        is kept until close(): a launch in flight may still use it).  One area: the stitch()
+        calls of an estimator must all go to the same stream."""
+        import torch
+        if self._mb_buf is None or self._mb_buf.numel() < nbytes:
+            if self._mb_buf is not None:
+                self._mb_old.append(self._mb_buf)
+            self._mb_buf = torch.empty(max(int(nbytes), 4), dtype=torch.uint8,
+                                       device=torch.device("cuda", self.device))
+        return self._mb_buf

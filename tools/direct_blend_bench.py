@@ -7,14 +7,20 @@ builds one per capture:
   (c) direct feather   Plan + set_blend(FEATHER) + mcs_stitch_direct      (mcs_direct_feather_*)
   (d) prepared feather Plan + set_blend(FEATHER) + mcs_plan_prepare + mcs_stitch_device +
                        mcs_plan_destroy: the only route to a feathered capture before (c)
+  (e) direct multi-band   Plan + set_blend(MULTIBAND) + mcs_stitch_direct_multiband, the work
+                          area allocated once outside the loop            (mcs_direct_mb_own_* +
+                                                                           mcs_direct_mb_tile_*)
+  (f) prepared multi-band Plan + set_blend(MULTIBAND) + mcs_plan_prepare + mcs_stitch_device +
+                          mcs_plan_destroy: the only route to a multi-band capture before (e)
 
 Every variant is timed with a host clock from before the plan is created to after a device
-synchronise (prepare is host-driven, so only this clock compares the four); (a) to (c) also with
-HIP events around the stitch call alone.  --warmup rounds, then --steps repeats with the variants
+synchronise (prepare is host-driven, so only this clock compares them); (a) to (c) and (e) also
+with HIP events around the stitch call alone (both launches of (e) together; a kernel trace of
+this tool gives them apart).  --warmup rounds, then --steps repeats with the variants
 alternated inside each round; median (min-max) in ms.  Prints the lines and, with --out, writes
 them to a file.
 
-    python tools/direct_blend_bench.py --out profiles/direct_feather_bench.txt
+    python tools/direct_blend_bench.py --out profiles/direct_multiband_bench.txt
 """
 import argparse
 import os
@@ -51,6 +57,7 @@ def main():
     strides = [t.numel() for t in d]
     probe = _capi.Plan(descs, w, h, C, _capi.MCS_INTER_LINEAR)
     ow, oh = probe.out_w, probe.out_h
+    mb_work = probe.direct_multiband_work_size()
     probe.close()
     pitch = (ow * C + 255) // 256 * 256
     out = torch.empty((oh, pitch), dtype=torch.uint8, device=dev)
@@ -72,20 +79,42 @@ def main():
             return (t1 - t0) * 1e3, ev0.elapsed_time(ev1)
         return run
 
-    def prepared():
+    def prepared(mode):
+        def run():
+            t0 = time.perf_counter()
+            plan = _capi.Plan(descs, w, h, C, _capi.MCS_INTER_LINEAR)
+            plan.set_blend(mode)
+            plan.prepare(stream)
+            plan.stitch_device(ptrs, strides, out.data_ptr(), pitch, pitch * oh, 1, stream)
+            torch.cuda.synchronize()
+            plan.close()
+            return (time.perf_counter() - t0) * 1e3, None
+        return run
+
+    # the multi-band work area: the caller's, allocated once (its size depends on the mosaic only)
+    work = torch.empty(mb_work, dtype=torch.uint8, device=dev)
+
+    def direct_multiband():
         t0 = time.perf_counter()
         plan = _capi.Plan(descs, w, h, C, _capi.MCS_INTER_LINEAR)
-        plan.set_blend(_capi.MCS_BLEND_FEATHER)
-        plan.prepare(stream)
-        plan.stitch_device(ptrs, strides, out.data_ptr(), pitch, pitch * oh, 1, stream)
+        plan.set_blend(_capi.MCS_BLEND_MULTIBAND)
+        ev0.record()
+        plan.stitch_direct_multiband(ptrs, strides, out.data_ptr(), pitch, pitch * oh, 1,
+                                     work.data_ptr(), work.numel(), stream)
+        ev1.record()
         torch.cuda.synchronize()
+        t1 = time.perf_counter()
         plan.close()
-        return (time.perf_counter() - t0) * 1e3, None
+        return (t1 - t0) * 1e3, ev0.elapsed_time(ev1)
 
     variants = [("a direct paste", direct(_capi.MCS_BLEND_NONE)),
                 ("b direct seam", direct(_capi.MCS_BLEND_SEAM)),
                 ("c direct feather", direct(_capi.MCS_BLEND_FEATHER)),
-                ("d prepared feather (prepare + stitch_device + destroy)", prepared)]
+                ("d prepared feather (prepare + stitch_device + destroy)",
+                 prepared(_capi.MCS_BLEND_FEATHER)),
+                ("e direct multi-band (work area: %d bytes)" % mb_work, direct_multiband),
+                ("f prepared multi-band (prepare + stitch_device + destroy)",
+                 prepared(_capi.MCS_BLEND_MULTIBAND))]
     host = {name: [] for name, _ in variants}
     devt = {name: [] for name, _ in variants}
     for step in range(args.warmup + args.steps):
@@ -105,18 +134,25 @@ def main():
     med = {name[0]: float(np.median(host[name])) for name, _ in variants}
     dmed = {name[0]: float(np.median(devt[name])) for name, _ in variants if devt[name]}
     d_min = float(np.min(host[variants[3][0]]))
+    f_min = float(np.min(host[variants[5][0]]))
     lines.append("c - b: host %.4f ms, device %.4f ms;  c - a: host %.4f ms, device %.4f ms;  "
                  "c / b: device %.2f" % (med["c"] - med["b"], dmed["c"] - dmed["b"],
                                          med["c"] - med["a"], dmed["c"] - dmed["a"],
                                          dmed["c"] / dmed["b"]))
     lines.append("bar (c median below d minimum): %.4f < %.4f: %s" % (
         med["c"], d_min, "holds" if med["c"] < d_min else "MISSED"))
+    lines.append("e - b: host %.4f ms, device %.4f ms;  e - a: host %.4f ms, device %.4f ms;  "
+                 "e / b: device %.2f" % (med["e"] - med["b"], dmed["e"] - dmed["b"],
+                                         med["e"] - med["a"], dmed["e"] - dmed["a"],
+                                         dmed["e"] / dmed["b"]))
+    lines.append("bar (e median below f minimum): %.4f < %.4f: %s" % (
+        med["e"], f_min, "holds" if med["e"] < f_min else "MISSED"))
     text = "\n".join(lines)
     print(text)
     if args.out:
         with open(args.out, "w") as f:
             f.write(text + "\n")
-    return 0 if med["c"] < d_min else 1
+    return 0 if med["c"] < d_min and med["e"] < f_min else 1
 
 
 if __name__ == "__main__":

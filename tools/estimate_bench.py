@@ -100,8 +100,16 @@ def estimate_cpu(frames, args):
 
 
 # --blend: the direct stitch's mode (_capi.MCS_BLEND_*) and its name in the printed line
-BLENDS = {"none": 0, "seam": 3, "feather": 1}
-BLEND_NAMES = {"none": "paste", "seam": "seam", "feather": "feather"}
+BLENDS = {"none": 0, "seam": 3, "feather": 1, "multiband": 2}
+BLEND_NAMES = {"none": "paste", "seam": "seam", "feather": "feather",
+               "multiband": "multi-band: mcs_stitch_direct_multiband"}
+
+
+def blend_args(blend):
+    """CaptureEstimator's arguments for --blend: multiband is its own switch, not a blend= mode."""
+    if blend == "multiband":
+        return dict(blend=0, multiband=True)
+    return dict(blend=BLENDS[blend])
 
 
 def bench_lens(w, h):
@@ -179,9 +187,10 @@ def main():
     ap.add_argument("--stitch-streams", action="store_true",
                     help="pipelined: each slot's stitches on a stream of their own (default: one "
                          "stitch stream)")
-    ap.add_argument("--blend", choices=("none", "seam", "feather"), default="none",
+    ap.add_argument("--blend", choices=("none", "seam", "feather", "multiband"), default="none",
                     help="with --stitch: blend mode of the capture's direct stitch (none: the "
-                         "paste; seam; feather: mcs_direct_feather_*)")
+                         "paste; seam; feather: mcs_direct_feather_*; multiband: "
+                         "mcs_stitch_direct_multiband, mcs_direct_mb_*)")
     ap.add_argument("--exposure", type=int, default=None, metavar="K",
                     help="with --stitch --pipelined --overlap (the in-library stitch): per-capture "
                          "exposure gains from the table-free overlap statistics on the 2^K grid "
@@ -284,7 +293,7 @@ def stitch_main(args, frames, truth, W, Hh, N):
     pitch = 8192 * 3
     out = torch.empty((2048, pitch), dtype=torch.uint8, device=dev)
     est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
-                                    blend=BLENDS[args.blend], lenses=args.lenses)
+                                    lenses=args.lenses, **blend_args(args.blend))
     ptrs = [t.data_ptr() for t in d]
     tot = {"upload": 0.0, "estimate": 0.0, "plan_stitch": 0.0}
     mpix = 0.0
@@ -357,6 +366,10 @@ def pipelined_main(args, frames, truth, W, Hh, N):
     B = max(1, args.batch)          # captures per rig job (and per frame set / output slot)
     if B > 1 and not (args.overlap and not args.python_stitch):
         raise SystemExit("--batch needs --overlap (rig jobs) and the in-library stitch")
+    if (args.blend == "multiband" and args.stitch_streams and
+            not (args.overlap and not args.python_stitch)):
+        # (the estimator's Python-issued stitch has ONE work area; every rig job has its own)
+        raise SystemExit("--blend multiband with --stitch-streams needs the in-library stitch")
     dev = torch.device("cuda", 0)
     host = []
     for f in frames:
@@ -383,8 +396,8 @@ def pipelined_main(args, frames, truth, W, Hh, N):
     for e in ev_done:
         e.record(sts[0])
     est = estimate.CaptureEstimator(N, W, Hh, 3, nfeatures=args.nfeatures, threads=args.threads,
-                                    captures_per_job=B, blend=BLENDS[args.blend],
-                                    exposure=args.exposure, lenses=args.lenses)
+                                    captures_per_job=B, exposure=args.exposure,
+                                    lenses=args.lenses, **blend_args(args.blend))
     pending = [None] * D          # plan of the capture last stitched from frame set / output i
     lat = []
 
