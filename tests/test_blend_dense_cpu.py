@@ -4,6 +4,7 @@ the FEATHER rule; every other tile keeps the multi-band values.  The GPU reprodu
 (tests/test_gpu_blend.py::test_multiband_more_than_eight_owners_degrades_to_feather)."""
 import numpy as np
 
+from blend_ref import dense_tiles as _dense_tiles
 from oracle import oracle
 
 
@@ -19,19 +20,6 @@ def _dense_rig(n=10, w=200, h=40, step=4, seed=11):
     cams = [images[label] for label in st.img_labels]
     plan = _capi.Plan([_stage_desc(sb) for sb in st.stitchers], w, h, 3, 1)
     return plan.describe(), cams
-
-
-def _dense_tiles(owner):
-    oh, ow = owner.shape
-    gx, gy = (ow + 31) // 32, (oh + 63) // 64
-    dense = np.zeros((gy, gx), bool)
-    for ty in range(gy):
-        for tx in range(gx):
-            y0, y1 = max(ty * 64 - 16, 0), min(ty * 64 + 80, oh)
-            x0, x1 = max(tx * 32 - 16, 0), min(tx * 32 + 48, ow)
-            o = np.unique(owner[y0:y1, x0:x1])
-            dense[ty, tx] = len(o[o != 255]) > 8
-    return dense
 
 
 def test_dense_tiles_take_the_feather_rule():
