@@ -564,15 +564,20 @@ class Plan:
         check(self._lib.mcs_plan_seam_stats(self._h, st.ctypes.data_as(ctypes.c_void_p)))
         return tuple(int(v) for v in st)
 
-    def stitch_device(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
-                      out_frame_stride: int, n_frames: int, stream: int = 0):
-        """Device-resident batch (raw device pointers, e.g. torch tensor data_ptr())."""
+    def _stitch(self, fn, cam_ptrs, cam_frame_strides, out_ptr, out_pitch, out_frame_stride,
+                n_frames, *extra, stream):
+        """One device stitch call: fn(plan, cameras, strides, mosaic, n_frames, *extra, stream)."""
         n = len(cam_ptrs)
         ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
         strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
-        check(self._lib.mcs_stitch_device(self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)),
-                                          int(out_pitch), int(out_frame_stride), int(n_frames),
-                                          ctypes.c_void_p(int(stream))))
+        check(fn(self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
+                 int(out_frame_stride), int(n_frames), *extra, ctypes.c_void_p(int(stream))))
+
+    def stitch_device(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
+                      out_frame_stride: int, n_frames: int, stream: int = 0):
+        """Device-resident batch (raw device pointers, e.g. torch tensor data_ptr())."""
+        self._stitch(self._lib.mcs_stitch_device, cam_ptrs, cam_frame_strides, out_ptr, out_pitch,
+                     out_frame_stride, n_frames, stream=stream)
 
     def stitch_direct(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
                       out_frame_stride: int, n_frames: int, stream: int = 0):
@@ -580,24 +585,16 @@ class Plan:
         exact map evaluated per pixel in the kernel) -- for a plan built for one capture, e.g.
         from per-frame homographies.  Paste, seam and feather plans (feather: one pass over
         the mosaic, mcs_direct_feather_*); multi-band needs stitch_device."""
-        n = len(cam_ptrs)
-        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
-        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
-        check(self._lib.mcs_stitch_direct(self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)),
-                                          int(out_pitch), int(out_frame_stride), int(n_frames),
-                                          ctypes.c_void_p(int(stream))))
+        self._stitch(self._lib.mcs_stitch_direct, cam_ptrs, cam_frame_strides, out_ptr, out_pitch,
+                     out_frame_stride, n_frames, stream=stream)
 
     def stitch_device_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
                              out_frame_stride: int, n_frames: int, stream: int = 0):
         """mcs_stitch_device_gained: stitch_device with the plan's gains (set_gains) applied
         inside the kernels -- the frames are only read; the mosaic is that of the pre-gained
         frames, bit for bit."""
-        n = len(cam_ptrs)
-        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
-        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
-        check(self._lib.mcs_stitch_device_gained(
-            self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
-            int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(stream))))
+        self._stitch(self._lib.mcs_stitch_device_gained, cam_ptrs, cam_frame_strides, out_ptr,
+                     out_pitch, out_frame_stride, n_frames, stream=stream)
 
     def direct_multiband_work_size(self) -> int:
         """mcs_direct_multiband_work_size: bytes of the device work area stitch_direct_multiband
@@ -606,15 +603,6 @@ class Plan:
         check(self._lib.mcs_direct_multiband_work_size(self._h, ctypes.byref(n)))
         return int(n.value)
 
-    def _stitch_direct_multiband(self, fn, cam_ptrs, cam_frame_strides, out_ptr, out_pitch,
-                                 out_frame_stride, n_frames, work_ptr, work_bytes, stream):
-        n = len(cam_ptrs)
-        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
-        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
-        check(fn(self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
-                 int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(work_ptr)),
-                 int(work_bytes), ctypes.c_void_p(int(stream))))
-
     def stitch_direct_multiband(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
                                 out_frame_stride: int, n_frames: int, work_ptr: int,
                                 work_bytes: int, stream: int = 0):
@@ -622,27 +610,23 @@ class Plan:
         tables (the same pixels as prepare + stitch_device).  work_ptr / work_bytes: a device
         work area of the caller of at least direct_multiband_work_size() bytes; it need not be
         initialised and may be reused by the next call on the same stream."""
-        self._stitch_direct_multiband(self._lib.mcs_stitch_direct_multiband, cam_ptrs,
-                                      cam_frame_strides, out_ptr, out_pitch, out_frame_stride,
-                                      n_frames, work_ptr, work_bytes, stream)
+        self._stitch(self._lib.mcs_stitch_direct_multiband, cam_ptrs, cam_frame_strides, out_ptr,
+                     out_pitch, out_frame_stride, n_frames, ctypes.c_void_p(int(work_ptr)),
+                     int(work_bytes), stream=stream)
 
     def stitch_direct_multiband_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int,
                                        out_pitch: int, out_frame_stride: int, n_frames: int,
                                        work_ptr: int, work_bytes: int, stream: int = 0):
         """mcs_stitch_direct_multiband_gained: the same with the plan's gains in the kernels."""
-        self._stitch_direct_multiband(self._lib.mcs_stitch_direct_multiband_gained, cam_ptrs,
-                                      cam_frame_strides, out_ptr, out_pitch, out_frame_stride,
-                                      n_frames, work_ptr, work_bytes, stream)
+        self._stitch(self._lib.mcs_stitch_direct_multiband_gained, cam_ptrs, cam_frame_strides,
+                     out_ptr, out_pitch, out_frame_stride, n_frames,
+                     ctypes.c_void_p(int(work_ptr)), int(work_bytes), stream=stream)
 
     def stitch_direct_gained(self, cam_ptrs, cam_frame_strides, out_ptr: int, out_pitch: int,
                              out_frame_stride: int, n_frames: int, stream: int = 0):
         """mcs_stitch_direct_gained: stitch_direct with the plan's gains inside the kernel."""
-        n = len(cam_ptrs)
-        ptrs = (ctypes.c_void_p * n)(*[int(p) for p in cam_ptrs])
-        strides = (ctypes.c_int64 * n)(*[int(s) for s in cam_frame_strides])
-        check(self._lib.mcs_stitch_direct_gained(
-            self._h, ptrs, strides, ctypes.c_void_p(int(out_ptr)), int(out_pitch),
-            int(out_frame_stride), int(n_frames), ctypes.c_void_p(int(stream))))
+        self._stitch(self._lib.mcs_stitch_direct_gained, cam_ptrs, cam_frame_strides, out_ptr,
+                     out_pitch, out_frame_stride, n_frames, stream=stream)
 
     def prepare(self, stream: int = 0):
         """Evaluate and store the plan's map tables on its device (once)."""

@@ -34,10 +34,10 @@ HSACO = os.path.join(HERE, f"mcs_kernels.{ARCH}.hsaco")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))
 CXX = os.environ.get("CXX", "g++")
-HOST_SRC = ["mcs_plan.cpp", "hip_rt.cpp", "mcs_runtime.cpp", "mcs_capi.cpp", "mcs_prepare.cpp",
-            "mcs_sweep_host.cpp", "mcs_launch.cpp", "mcs_features.cpp", "mcs_stream.cpp",
-            "mcs_seam.cpp", "mcs_refine.cpp", "mcs_group.cpp", "mcs_rig.cpp", "mcs_chain.cpp",
-            "mcs_gain.cpp"]
+HOST_SRC = ["mcs_plan.cpp", "hip_rt.cpp", "mcs_runtime.cpp", "mcs_capi.cpp", "mcs_stitch.cpp",
+            "mcs_prepare.cpp", "mcs_sweep_host.cpp", "mcs_launch.cpp", "mcs_features.cpp",
+            "mcs_stream.cpp", "mcs_seam.cpp", "mcs_refine.cpp", "mcs_group.cpp", "mcs_rig.cpp",
+            "mcs_chain.cpp", "mcs_gain.cpp"]
 HEADERS = ["mcs_kparams.h", "mcs_dev.h", "mcs_fparams.h", "mcs_common.h", "hip_rt.h", "mcs_blend.h",
            "mcs_mb_prep.h", "mcs_mb_levels.h", "mcs_mb_bands.h", "mcs_mb_blend.h",
            "mcs_gain.h", "mcs_ransac_core.h",

@@ -1,4 +1,5 @@
-// mcs_capi.cpp -- the extern "C" boundary of libmcs.so (declared in include/mcs.h).
+// mcs_capi.cpp -- the extern "C" boundary of libmcs.so (declared in include/mcs.h), but for the
+// device-resident stitch entry points (mcs_stitch.cpp) and those of the seams (mcs_seam.cpp).
 //
 // Replaces, for a calibrated chain, the per-frame work of Stitcher.stitch
 // (PostScripts/Stitcher/StitcherClass.py:114-136).  No exception crosses this boundary: every
@@ -429,265 +430,6 @@ int mcs_resize_linear_device(const uint8_t *d_src, int src_w, int src_h, int64_t
                          dfs, channels, n_frames, (hipStream_t)stream);
 }
 
-// Kernel parameters of a device-resident batch (mcs_stitch_device / mcs_stitch_direct).
-static int device_kparams(const mcs_plan *p, const uint8_t *const *d_cams,
-                          const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                          int64_t out_frame_stride, int n_frames, mcs::KParams *kp)
-{
-    if (!p || !d_cams || !d_out) return mcs::fail(MCS_E_INVALID, "NULL plan/d_cams/d_out");
-    if (n_frames < 0 || n_frames > 65535) return mcs::fail(MCS_E_INVALID, "n_frames=%d", n_frames);
-    const int C = p->fd.channels;
-    if (out_pitch < (int64_t)p->fd.out_w * C)
-        return mcs::fail(MCS_E_INVALID, "out_pitch %lld < row bytes %lld", (long long)out_pitch,
-                         (long long)p->fd.out_w * C);
-    *kp = p->kp;
-    bool need[MCS_MAX_CAMS];
-    need_mask(p->fd, need);
-    for (int i = 0; i < p->fd.n_cams; i++) {
-        if (need[i] && !d_cams[i]) return mcs::fail(MCS_E_INVALID, "d_cams[%d] NULL", i);
-        kp->cams[i] = d_cams[i];
-        kp->cam_fstride[i] = cam_frame_stride ? cam_frame_stride[i]
-                                              : (int64_t)p->fd.cam_w[i] * p->fd.cam_h[i] * C;
-    }
-    kp->out = d_out;
-    kp->out_pitch = out_pitch;
-    kp->out_fstride = out_frame_stride ? out_frame_stride : out_pitch * p->fd.out_h;
-    return MCS_OK;
-}
-
-// The device entry points read caller memory and never write it, so they cannot apply gains.
-static int refuse_gains(const mcs_plan *p, const char *entry)
-{
-    if (!p || !p->gains_on) return MCS_OK;
-    return mcs::fail(MCS_E_UNSUPPORTED, "%s reads the caller's frames and never writes them: on a "
-                     "plan with gains (mcs_plan_set_gains) apply them to the frames first with "
-                     "mcs_gain_apply_device and stitch with a plan without gains", entry);
-}
-
-int mcs_stitch_device(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
-                      uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,
-                      void *stream)
-{
-    const int rc = refuse_gains(p, "mcs_stitch_device");
-    if (rc) return rc;
-    return mcs::stitch_device_frames(p, d_cams, cam_frame_stride, d_out, out_pitch,
-                                     out_frame_stride, n_frames, stream);
-}
-
-}  // extern "C"
-
-// mcs_stitch_device(_gained) after the refusals: the checks, the device, the launch.
-static int stitch_device_launch(mcs_plan *p, const uint8_t *const *d_cams,
-                                const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                                int64_t out_frame_stride, int n_frames, void *stream, bool gained)
-{
-    mcs::KParams kp;
-    int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                            n_frames, &kp);
-    if (rc) return rc;
-    const mcs::Entry A(p->device);
-    if (A.status) return A.status;
-    // (identity gains, or none: exactly the ungained launch)
-    return launch_stitch(A, p, kp, n_frames, (hipStream_t)stream, gained && gains_active(p));
-}
-
-int mcs::stitch_device_frames(mcs_plan *p, const uint8_t *const *d_cams,
-                              const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                              int64_t out_frame_stride, int n_frames, void *stream)
-{
-    return stitch_device_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                                n_frames, stream, false);
-}
-
-// mcs_stitch_direct(_gained) after the refusals.  gained: the _g kernels with the plan's q as of
-// this call in their arguments, unless every used camera's q is the identity.
-static int stitch_direct_launch(mcs_plan *p, const uint8_t *const *d_cams,
-                                const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                                int64_t out_frame_stride, int n_frames, void *stream, bool gained)
-{
-    mcs::KParams kp;
-    int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                            n_frames, &kp);
-    if (rc) return rc;
-    if (p->blend != MCS_BLEND_NONE && p->blend != MCS_BLEND_SEAM && p->blend != MCS_BLEND_FEATHER)
-        return mcs::fail(MCS_E_UNSUPPORTED, "mcs_stitch_direct renders paste / seam / feather "
-                         "plans; multi-band plans need their prepared tables (mcs_stitch_device)");
-    const bool feather = p->blend == MCS_BLEND_FEATHER;
-    gained = gained && gains_active(p);
-    if (gained) fill_gain_q(p, &kp);
-    if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames == 0) return MCS_OK;
-    const mcs::Entry A(p->device);
-    if (A.status) return A.status;
-    const Kernels *k = nullptr;
-    rc = kernels(A, p->device, &k);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = upload_plan_tables(A, p, s);   // (cylinder / table plans: their device tables, once)
-    if (rc) return rc;
-    kp.cyl_tab = p->kp.cyl_tab;
-    kp.map_tab = p->kp.map_tab;
-    kp.lens_tab = p->kp.lens_tab;
-    kp.seam_hint = p->kp.seam_hint;
-    const int gx = (p->fd.out_w + mcs::kTileW - 1) / mcs::kTileW;
-    const int gy = (p->fd.out_h + mcs::kTileH - 1) / mcs::kTileH;
-    // one frame stride for every camera per launch (the kernel's walk), else frame by frame
-    bool uniform = true;
-    for (int j = 0; j < p->fd.n_stages; j++)
-        uniform = uniform && kp.cam_fstride[p->fd.st[j].cam] == kp.cam_fstride[0];
-    const int runs = uniform ? 1 : n_frames;
-    for (int f = 0; f < runs; f++) {
-        mcs::KDirectArgs args;
-        args.P = kp;
-        if (!uniform) {
-            for (int i = 0; i < p->fd.n_cams; i++)
-                args.P.cams[i] = kp.cams[i] ? kp.cams[i] + (int64_t)f * kp.cam_fstride[i] : nullptr;
-            args.P.out = kp.out + (int64_t)f * kp.out_fstride;
-        }
-        const bool off32 = offset_base(p, args.P, &args.P.base);
-        args.fallback = nullptr;   // every tile
-        args.n_frames = uniform ? n_frames : 1;
-        args.pad_ = 0;
-        const unsigned fy = (unsigned)((args.n_frames + mcs::kDirectFrames - 1) / mcs::kDirectFrames);
-        // (feather: the one-pass blend kernel over the same grid; it addresses frames by pointer)
-        const hipFunction_t fn =
-            feather ? (gained ? k->direct_feather_g : k->direct_feather)[p->fd.channels][p->fd.interp]
-                    : (gained ? k->direct_g : k->direct)[p->fd.channels][p->fd.interp][off32 ? 1 : 0];
-        rc = launch_args(A, fn, (unsigned)(gx * gy), fy, mcs::kWave, mcs::kWavesPerBlock, &args,
-                         sizeof(args), s);
-        if (rc) return rc;
-    }
-    return MCS_OK;
-}
-
-// mcs_stitch_direct_multiband(_gained) after the gains refusal: two launches per run of frames
-// (csrc/mcs_direct_mb.hip), the caller's work area between them.
-static int stitch_direct_mb_launch(mcs_plan *p, const uint8_t *const *d_cams,
-                                   const int64_t *cam_frame_stride, uint8_t *d_out,
-                                   int64_t out_pitch, int64_t out_frame_stride, int n_frames,
-                                   void *d_work, int64_t work_bytes, void *stream, bool gained)
-{
-    mcs::KParams kp;
-    int rc = device_kparams(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                            n_frames, &kp);
-    if (rc) return rc;
-    if (p->blend != MCS_BLEND_MULTIBAND)
-        return mcs::fail(MCS_E_INVALID, "mcs_stitch_direct_multiband renders multi-band plans "
-                         "(mcs_plan_set_blend MCS_BLEND_MULTIBAND); paste / seam / feather plans "
-                         "are mcs_stitch_direct's");
-    if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames == 0) return MCS_OK;
-    const int64_t need = mcs::direct_mb_work_bytes(kp.out_w, kp.out_h);
-    if (!d_work || work_bytes < need)
-        return mcs::fail(MCS_E_INVALID, "mcs_stitch_direct_multiband: the work area (%s, %lld "
-                         "bytes) must hold %lld bytes (mcs_direct_multiband_work_size)",
-                         d_work ? "given" : "NULL", (long long)work_bytes, (long long)need);
-    gained = gained && gains_active(p);
-    if (gained) fill_gain_q(p, &kp);
-    const mcs::Entry A(p->device);
-    if (A.status) return A.status;
-    const Kernels *k = nullptr;
-    rc = kernels(A, p->device, &k);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    rc = upload_plan_tables(A, p, s);   // (cylinder / lensed plans: their device tables, once)
-    if (rc) return rc;
-    kp.cyl_tab = p->kp.cyl_tab;
-    kp.map_tab = p->kp.map_tab;
-    kp.lens_tab = p->kp.lens_tab;
-    kp.seam_hint = p->kp.seam_hint;
-    kp.base = nullptr;   // (the kernels address frames by pointer)
-    const int C = p->fd.channels, I = p->fd.interp;
-    const int gx = (kp.out_w + mcs::kTileW - 1) / mcs::kTileW;
-    const int gy = (kp.out_h + mcs::kTileH - 1) / mcs::kTileH;
-    // one frame stride for every camera per launch, else frame by frame (as mcs_stitch_direct)
-    bool uniform = true;
-    for (int j = 0; j < p->fd.n_stages; j++)
-        uniform = uniform && kp.cam_fstride[p->fd.st[j].cam] == kp.cam_fstride[0];
-    const int runs = uniform ? 1 : n_frames;
-    for (int f = 0; f < runs; f++) {
-        mcs::KDirectMbArgs args;
-        args.P = kp;
-        if (!uniform) {
-            for (int i = 0; i < p->fd.n_cams; i++)
-                args.P.cams[i] = kp.cams[i] ? kp.cams[i] + (int64_t)f * kp.cam_fstride[i] : nullptr;
-            args.P.out = kp.out + (int64_t)f * kp.out_fstride;
-        }
-        args.cells = static_cast<uint32_t *>(d_work);
-        args.n_frames = uniform ? n_frames : 1;
-        args.gxb = (kp.out_w + mcs::kBlendTileW - 1) / mcs::kBlendTileW;
-        args.gyb = (kp.out_h + mcs::kBlendTileH - 1) / mcs::kBlendTileH;
-        args.cgx = mcs::dmb_cells(kp.out_w);
-        args.cgy = mcs::dmb_cells(kp.out_h);
-        args.pad_ = 0;
-        const unsigned fy = (unsigned)((args.n_frames + mcs::kDirectFrames - 1) / mcs::kDirectFrames);
-        rc = launch_args(A, k->direct_mb_own[gained][C][I], (unsigned)(gx * gy), fy, mcs::kWave,
-                         mcs::kWavesPerBlock, &args, sizeof(args), s);
-        if (rc) return rc;
-        rc = launch_args(A, k->direct_mb_tile[gained][C][I], (unsigned)(args.gxb * args.gyb),
-                         (unsigned)args.n_frames, mcs::kDmbTileThreads, 1, &args, sizeof(args), s, 1,
-                         (unsigned)mcs::dmb_lds(C).bytes);
-        if (rc) return rc;
-    }
-    return MCS_OK;
-}
-
-extern "C" {
-
-int mcs_direct_multiband_work_size(const mcs_plan *p, int64_t *bytes)
-{
-    mcs::clear_error();
-    if (!p || !bytes) return mcs::fail(MCS_E_INVALID, "NULL plan/bytes");
-    *bytes = mcs::direct_mb_work_bytes(p->fd.out_w, p->fd.out_h);
-    return MCS_OK;
-}
-
-int mcs_stitch_direct_multiband(mcs_plan *p, const uint8_t *const *d_cams,
-                                const int64_t *cam_frame_stride, uint8_t *d_out,
-                                int64_t out_pitch, int64_t out_frame_stride, int n_frames,
-                                void *d_work, int64_t work_bytes, void *stream)
-{
-    const int rc = refuse_gains(p, "mcs_stitch_direct_multiband");
-    if (rc) return rc;
-    return stitch_direct_mb_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                                   n_frames, d_work, work_bytes, stream, false);
-}
-
-int mcs_stitch_direct_multiband_gained(mcs_plan *p, const uint8_t *const *d_cams,
-                                       const int64_t *cam_frame_stride, uint8_t *d_out,
-                                       int64_t out_pitch, int64_t out_frame_stride, int n_frames,
-                                       void *d_work, int64_t work_bytes, void *stream)
-{
-    return stitch_direct_mb_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                                   n_frames, d_work, work_bytes, stream, true);
-}
-
-int mcs_stitch_direct(mcs_plan *p, const uint8_t *const *d_cams, const int64_t *cam_frame_stride,
-                      uint8_t *d_out, int64_t out_pitch, int64_t out_frame_stride, int n_frames,
-                      void *stream)
-{
-    const int rc = refuse_gains(p, "mcs_stitch_direct");
-    if (rc) return rc;
-    return stitch_direct_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                                n_frames, stream, false);
-}
-
-// The fused forms: the plan's gains inside the kernels, on the taps (csrc/mcs_dev.h gain_half);
-// the caller's frames are only read.
-int mcs_stitch_device_gained(mcs_plan *p, const uint8_t *const *d_cams,
-                             const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                             int64_t out_frame_stride, int n_frames, void *stream)
-{
-    return stitch_device_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                                n_frames, stream, true);
-}
-
-int mcs_stitch_direct_gained(mcs_plan *p, const uint8_t *const *d_cams,
-                             const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                             int64_t out_frame_stride, int n_frames, void *stream)
-{
-    return stitch_direct_launch(p, d_cams, cam_frame_stride, d_out, out_pitch, out_frame_stride,
-                                n_frames, stream, true);
-}
-
 int mcs_plan_prepare(mcs_plan *p, void *stream)
 {
     if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
@@ -795,171 +537,6 @@ int mcs_lens_unmap_host(const double *K, const double *dist, int n_dist, const d
         uv[2 * i] = u;
         uv[2 * i + 1] = v;
     }
-    return MCS_OK;
-}
-
-int mcs_plan_find_seams(mcs_plan *p, const uint8_t *const *cams, int method, int scale_log2)
-{
-    mcs::clear_error();
-    if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
-    for (int64_t &v : p->seam_stats) v = 0;   // (only the device max-flow fills them in)
-    if (method != MCS_SEAM_DISTANCE && method != MCS_SEAM_GRAPHCUT)
-        return mcs::fail(MCS_E_INVALID, "seam method %d", method);
-    if (method == MCS_SEAM_GRAPHCUT && (!cams || scale_log2 < 0 || scale_log2 > 4))
-        return mcs::fail(MCS_E_INVALID, "graph-cut seams need cams and scale_log2 in 0..4");
-    const mcs::Entry A(p->device);
-    if (A.status) return A.status;
-    release_tables(A, p);
-    if (p->d_seam) (void)A->hipFree(p->d_seam);
-    p->d_seam = nullptr;
-    p->kp.seam_hint = nullptr;
-    p->seam_lab.clear();
-    p->seam_w = p->seam_h = p->seam_k = 0;
-    if (method == MCS_SEAM_DISTANCE || p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
-    int rc = ensure_stream(A, p);
-    if (rc == MCS_OK) rc = ensure_host_buffers(A, p);
-    if (rc == MCS_OK) rc = upload_plan_tables(A, p, p->stream);
-    const Kernels *k = nullptr;
-    if (rc == MCS_OK) rc = kernels(A, p->device, &k);
-    if (rc) return rc;
-    const int C = p->fd.channels, n = p->fd.n_cams;
-    for (int i = 0; i < n; i++) {
-        if (!cams[i]) return mcs::fail(MCS_E_INVALID, "NULL cams[%d]", i);
-        HIP_TRY(A->hipMemcpyAsync(p->d_cams[i], cams[i],
-                                  (size_t)p->fd.cam_w[i] * p->fd.cam_h[i] * C,
-                                  hipMemcpyHostToDevice, p->stream));
-    }
-    const int kk = scale_log2;
-    const int gw = (p->fd.out_w + (1 << kk) - 1) >> kk, gh = (p->fd.out_h + (1 << kk) - 1) >> kk;
-    const size_t np = (size_t)gw * gh;
-    mcs::KSeamArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P = p->kp;
-    for (int i = 0; i < n; i++) {
-        a.P.cams[i] = p->d_cams[i];
-        a.P.cam_fstride[i] = 0;
-    }
-    a.gw = gw;
-    a.gh = gh;
-    a.k = kk;
-    std::vector<uint8_t> lab(np), smp;   // (smp: host Dinic only)
-    std::vector<uint16_t> cov(np);
-    static const char what[] = "seam finding";
-    mcs::Scratch sc(A, p->stream);
-    HIP_TRY_AS(what, sc.dev(&a.label, np));
-    HIP_TRY_AS(what, sc.dev(&a.cov, np));
-    HIP_TRY_AS(what, sc.dev(&a.samples, np * C * n));
-    HIP_TRY_AS(what, A->hipMemsetAsync(a.samples, 0, np * C * n, p->stream));
-    rc = launch_args(A, k->seam_sample[C][p->fd.interp], (unsigned)((np + 255) / 256), 1, 256, 1,
-                     &a, sizeof(a), p->stream);
-    if (rc) return rc;
-    // the pairwise cuts: push-relabel on the device (default), or the host Dinic
-    // (MCS_SEAM_FLOW=host; the checker of the device path)
-    static const bool host_flow =
-        getenv("MCS_SEAM_FLOW") && !strcmp(getenv("MCS_SEAM_FLOW"), "host");
-    HIP_TRY_AS(what, A->hipMemcpyAsync(cov.data(), a.cov, np * 2, hipMemcpyDeviceToHost,
-                                       p->stream));
-    if (host_flow) {
-        HIP_TRY_AS(what, A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost,
-                                           p->stream));
-        smp.resize(np * C * n);
-        HIP_TRY_AS(what, A->hipMemcpyAsync(smp.data(), a.samples, np * C * n,
-                                           hipMemcpyDeviceToHost, p->stream));
-    }
-    HIP_TRY_AS(what, sc.sync());
-    if (host_flow) {
-        rc = mcs::seam_graphcut(n, gw, gh, lab.data(), cov.data(), smp.data(), C);
-        if (rc) return rc;
-        HIP_TRY_AS(what, A->hipMemcpyAsync(a.label, lab.data(), np, hipMemcpyHostToDevice,
-                                           p->stream));
-    } else {
-        rc = mcs::seam_graphcut_device(p->device, p->stream, n, gw, gh, a.label, a.cov, a.samples,
-                                       C, cov.data(), p->seam_stats);
-        if (rc) return rc;
-        HIP_TRY_AS(what, A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost,
-                                           p->stream));
-    }
-    HIP_TRY_AS(what, sc.sync());
-    p->d_seam = sc.keep(a.label);   // the device labels (the seam grid the stitch kernels read)
-    p->seam_lab.swap(lab);
-    p->seam_w = gw;
-    p->seam_h = gh;
-    p->seam_k = kk;
-    p->kp.seam_hint = p->d_seam;
-    p->kp.seam_w = gw;
-    p->kp.seam_shift = kk;
-    return MCS_OK;
-}
-
-int mcs_seam_graphcut_host(int n_cams, int gw, int gh, uint8_t *labels, const uint16_t *cover,
-                           const uint8_t *samples, int channels)
-{
-    mcs::clear_error();
-    if (!labels || !cover || !samples) return mcs::fail(MCS_E_INVALID, "NULL input");
-    if (n_cams < 1 || n_cams > 16 || gw < 1 || gh < 1 || channels < 1 || channels > 4 ||
-        (int64_t)gw * gh > (int64_t)1 << 28)
-        return mcs::fail(MCS_E_INVALID, "n_cams %d, grid %dx%d, channels %d", n_cams, gw, gh,
-                         channels);
-    return mcs::seam_graphcut(n_cams, gw, gh, labels, cover, samples, channels);
-}
-
-// mcs_seam_graphcut_device on its stream s, after the checks.
-static int graphcut_on_stream(const Api *A, hipStream_t s, int n_cams, int gw, int gh,
-                              uint8_t *labels, const uint16_t *cover, const uint8_t *samples,
-                              int channels, int device, int64_t *stats)
-{
-    static const char what[] = "seam graph cut";
-    const size_t np = (size_t)gw * gh, sb = np * n_cams * channels;
-    mcs::Scratch sc(A, s);
-    uint8_t *buf = nullptr;
-    HIP_TRY_AS(what, sc.dev(&buf, np * 3 + sb + 16));
-    uint8_t *d_lab = buf, *d_smp = buf + np * 3 + 16;
-    uint16_t *d_cov = reinterpret_cast<uint16_t *>(buf + ((np + 7) & ~(size_t)7));
-    HIP_TRY_AS(what, A->hipMemcpyAsync(d_lab, labels, np, hipMemcpyHostToDevice, s));
-    HIP_TRY_AS(what, A->hipMemcpyAsync(d_cov, cover, np * 2, hipMemcpyHostToDevice, s));
-    HIP_TRY_AS(what, A->hipMemcpyAsync(d_smp, samples, sb, hipMemcpyHostToDevice, s));
-    const int rc = mcs::seam_graphcut_device(device, s, n_cams, gw, gh, d_lab, d_cov, d_smp,
-                                             channels, cover, stats);
-    if (rc) return rc;
-    HIP_TRY_AS(what, A->hipMemcpyAsync(labels, d_lab, np, hipMemcpyDeviceToHost, s));
-    HIP_TRY_AS(what, sc.sync());
-    // (this entry point has always synchronised twice here: the runtime sees the calls it saw)
-    HIP_TRY_AS(what, sc.sync());
-    return MCS_OK;
-}
-
-int mcs_seam_graphcut_device(int n_cams, int gw, int gh, uint8_t *labels, const uint16_t *cover,
-                             const uint8_t *samples, int channels, int device, int64_t *stats)
-{
-    mcs::clear_error();
-    if (!labels || !cover || !samples) return mcs::fail(MCS_E_INVALID, "NULL input");
-    if (n_cams < 1 || n_cams > 16 || gw < 1 || gh < 1 || channels < 1 || channels > 4 ||
-        (int64_t)gw * gh > (int64_t)1 << 28)
-        return mcs::fail(MCS_E_INVALID, "n_cams %d, grid %dx%d, channels %d", n_cams, gw, gh,
-                         channels);
-    const mcs::Entry A(device);
-    if (A.status) return A.status;
-    hipStream_t s = nullptr;
-    HIP_TRY(A->hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    const int rc = graphcut_on_stream(A, s, n_cams, gw, gh, labels, cover, samples, channels,
-                                      device, stats);
-    (void)A->hipStreamDestroy(s);
-    return rc;
-}
-
-int mcs_plan_seam_stats(const mcs_plan *p, int64_t *stats)
-{
-    if (!p || !stats) return mcs::fail(MCS_E_INVALID, "NULL plan/stats");
-    for (int j = 0; j < 5; j++) stats[j] = p->seam_stats[j];
-    return MCS_OK;
-}
-
-int mcs_plan_seam_labels(const mcs_plan *p, uint8_t *out, int *w, int *h)
-{
-    if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
-    if (w) *w = p->seam_w;
-    if (h) *h = p->seam_h;
-    if (out && !p->seam_lab.empty()) memcpy(out, p->seam_lab.data(), p->seam_lab.size());
     return MCS_OK;
 }
 

@@ -66,11 +66,12 @@ int features_stream_wait(int device, void *event);
 // The HIP device a plan was created for (its tables, buffers and side streams live there).
 int plan_device(const mcs_plan *plan);
 
-// mcs_stitch_device without its refusal of plans with gains: for callers inside libmcs that own
-// the frames and have applied the gains themselves (the stream's slot buffers).
+// mcs_stitch_device(_gained) (mcs_stitch.cpp) without the refusal of plans with gains: for callers
+// inside libmcs that own the frames and have applied the gains themselves (the stream's slots).
 int stitch_device_frames(mcs_plan *plan, const uint8_t *const *d_cams,
                          const int64_t *cam_frame_stride, uint8_t *d_out, int64_t out_pitch,
-                         int64_t out_frame_stride, int n_frames, void *stream);
+                         int64_t out_frame_stride, int n_frames, void *stream,
+                         bool gained = false);
 // The gain kernel on `stream` of the plan's device (mcs_gain.cpp): q, or the device value *d_q
 // read when the kernel runs.
 int gain_apply_frames(const mcs_plan *plan, const uint8_t *d_src, uint8_t *d_dst, int64_t bytes,

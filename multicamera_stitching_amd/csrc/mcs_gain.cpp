@@ -148,8 +148,7 @@ int enqueue_direct_stats(const Api *A, mcs_plan *p, const uint8_t *const *d_cams
     a.P = p->kp;
     for (int i = 0; i < n; i++) {
         a.P.cams[i] = d_cams[i];
-        a.P.cam_fstride[i] = cam_frame_stride ? cam_frame_stride[i]
-                                              : (int64_t)p->fd.cam_w[i] * p->fd.cam_h[i] * C;
+        a.P.cam_fstride[i] = cam_fstride(p->fd, cam_frame_stride, i);
     }
     a.P.out = nullptr;
     a.stats = d_stats;
@@ -394,8 +393,7 @@ int mcs_plan_overlap_stats(mcs_plan *p, const uint8_t *const *d_cams,
     memset(&a, 0, sizeof(a));
     for (int i = 0; i < n; i++) {
         a.cams[i] = d_cams[i];
-        a.cam_fstride[i] = cam_frame_stride ? cam_frame_stride[i]
-                                            : (int64_t)p->fd.cam_w[i] * p->fd.cam_h[i] * C;
+        a.cam_fstride[i] = cam_fstride(p->fd, cam_frame_stride, i);
         a.cam_w[i] = p->fd.cam_w[i];
         a.cam_h[i] = p->fd.cam_h[i];
     }

@@ -427,6 +427,20 @@ void fill_gain_q(const mcs_plan *p, mcs::KParams *kp)
         kp->gain_q[i] = p->gains_on && i < p->fd.n_cams ? p->gain_q[i] : (uint16_t)256;
 }
 
+// All five for every caller.  A call's KParams starts as a copy of p->kp, taken before
+// upload_plan_tables / prepare ran for it, and those set cyl_tab, map_tab, lens_tab and (sweep
+// plans) skip on first use; seam_hint changes only in mcs_plan_find_seams.  A pointer that the
+// call's path left alone is copied onto an equal one: no caller keeps a list of its own.
+// (launch_stitch below still copies its four by hand.)
+void plan_table_pointers(const mcs_plan *p, mcs::KParams *P)
+{
+    P->cyl_tab = p->kp.cyl_tab;
+    P->map_tab = p->kp.map_tab;
+    P->lens_tab = p->kp.lens_tab;
+    P->seam_hint = p->kp.seam_hint;
+    P->skip = p->kp.skip;
+}
+
 int launch_stitch(const Api *A, mcs_plan *p, const mcs::KParams &kp, int n_frames, hipStream_t s,
                   bool gained)
 {

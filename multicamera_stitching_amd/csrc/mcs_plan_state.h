@@ -1,6 +1,6 @@
 // mcs_plan_state.h -- the plan behind the C ABI's mcs_plan handle, and the host functions that
 // build its tables (mcs_prepare.cpp, mcs_sweep_host.cpp) and schedule its launches
-// (mcs_launch.cpp) for the entry points in mcs_capi.cpp.  Host only.
+// (mcs_launch.cpp) for the entry points (mcs_capi.cpp, mcs_stitch.cpp, mcs_seam.cpp).  Host only.
 #pragma once
 
 #include <stdint.h>
@@ -249,6 +249,34 @@ void band_args(const mcs_plan *p, const KParams &P, KMbBandArgs &a);
 int launch_resize(const Api *A, const Kernels *k, const uint8_t *src, int sw, int sh,
                   int64_t src_pitch, int64_t src_fstride, uint8_t *dst, int dw, int dh,
                   int64_t dst_pitch, int64_t dst_fstride, int C, int n_frames, hipStream_t s);
+// Camera i's frame stride in bytes: the caller's, or without one its frames back to back.
+inline int64_t cam_fstride(const mcs_flat_desc &fd, const int64_t *strides, int i)
+{
+    return strides ? strides[i] : (int64_t)fd.cam_w[i] * fd.cam_h[i] * fd.channels;
+}
+// The plan's device-table pointers into a call's P, after upload_plan_tables / prepare.
+void plan_table_pointers(const mcs_plan *p, KParams *P);
+// The frame runs of a batch.  The kernels walk the captures of a launch with one frame stride:
+// when every used camera has cam_fstride[0], body(kp, n_frames) once; else body(P, 1) per capture
+// f with P's cams (a NULL one stays NULL) and out advanced to capture f, cam_fstride and
+// out_fstride as given.  Returns the first status that is not MCS_OK.
+template <class Body>
+int for_frame_runs(const mcs_plan *p, const KParams &kp, int n_frames, Body body)
+{
+    bool uniform = true;
+    for (int j = 0; j < p->fd.n_stages; j++)
+        uniform = uniform && kp.cam_fstride[p->fd.st[j].cam] == kp.cam_fstride[0];
+    if (uniform) return body(kp, n_frames);
+    KParams P = kp;
+    for (int f = 0; f < n_frames; f++) {
+        for (int i = 0; i < p->fd.n_cams; i++)
+            P.cams[i] = kp.cams[i] ? kp.cams[i] + (int64_t)f * kp.cam_fstride[i] : nullptr;
+        P.out = kp.out + (int64_t)f * kp.out_fstride;
+        const int rc = body(P, 1);
+        if (rc) return rc;
+    }
+    return MCS_OK;
+}
 // gained: the _g kernels for every launch of the batch, with the plan's gain_q as of this call in
 // their kernel arguments (mcs_stitch_device_gained); the caller has ruled out sweep plans.
 int launch_stitch(const Api *A, mcs_plan *p, const KParams &kp, int n_frames, hipStream_t s,

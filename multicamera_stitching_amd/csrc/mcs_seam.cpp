@@ -6,7 +6,7 @@
 // mcs_features.hip), or here on the host with Dinic's algorithm (seam_graphcut: the C-ABI's
 // mcs_seam_graphcut_host, and the cross-check of the device path).  Specification in
 // oracle/orc_seam.c (restated there with a third max-flow algorithm); all return the source side
-// of the minimal minimum cut, which every maximum flow shares.
+// of the minimal minimum cut, which every maximum flow shares.  The entry points: the file's end.
 #include <algorithm>
 #include <chrono>
 #include <cstdlib>
@@ -16,6 +16,7 @@
 
 #include "mcs_common.h"
 #include "mcs_feat_int.h"
+#include "mcs_plan_state.h"
 #include "mcs_scratch.h"
 
 namespace {
@@ -288,3 +289,174 @@ int seam_graphcut_device(int device, hipStream_t s, int n_cams, int gw, int gh, 
 }
 
 }  // namespace mcs
+
+using namespace mcs::host;
+
+extern "C" {
+
+int mcs_plan_find_seams(mcs_plan *p, const uint8_t *const *cams, int method, int scale_log2)
+{
+    mcs::clear_error();
+    if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
+    for (int64_t &v : p->seam_stats) v = 0;   // (only the device max-flow fills them in)
+    if (method != MCS_SEAM_DISTANCE && method != MCS_SEAM_GRAPHCUT)
+        return mcs::fail(MCS_E_INVALID, "seam method %d", method);
+    if (method == MCS_SEAM_GRAPHCUT && (!cams || scale_log2 < 0 || scale_log2 > 4))
+        return mcs::fail(MCS_E_INVALID, "graph-cut seams need cams and scale_log2 in 0..4");
+    const mcs::Entry A(p->device);
+    if (A.status) return A.status;
+    release_tables(A, p);
+    if (p->d_seam) (void)A->hipFree(p->d_seam);
+    p->d_seam = nullptr;
+    p->kp.seam_hint = nullptr;
+    p->seam_lab.clear();
+    p->seam_w = p->seam_h = p->seam_k = 0;
+    if (method == MCS_SEAM_DISTANCE || p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
+    int rc = ensure_stream(A, p);
+    if (rc == MCS_OK) rc = ensure_host_buffers(A, p);
+    if (rc == MCS_OK) rc = upload_plan_tables(A, p, p->stream);
+    const Kernels *k = nullptr;
+    if (rc == MCS_OK) rc = kernels(A, p->device, &k);
+    if (rc) return rc;
+    const int C = p->fd.channels, n = p->fd.n_cams;
+    for (int i = 0; i < n; i++) {
+        if (!cams[i]) return mcs::fail(MCS_E_INVALID, "NULL cams[%d]", i);
+        HIP_TRY(A->hipMemcpyAsync(p->d_cams[i], cams[i],
+                                  (size_t)p->fd.cam_w[i] * p->fd.cam_h[i] * C,
+                                  hipMemcpyHostToDevice, p->stream));
+    }
+    const int kk = scale_log2;
+    const int gw = (p->fd.out_w + (1 << kk) - 1) >> kk, gh = (p->fd.out_h + (1 << kk) - 1) >> kk;
+    const size_t np = (size_t)gw * gh;
+    mcs::KSeamArgs a;
+    memset(&a, 0, sizeof(a));
+    a.P = p->kp;
+    for (int i = 0; i < n; i++) {
+        a.P.cams[i] = p->d_cams[i];
+        a.P.cam_fstride[i] = 0;
+    }
+    a.gw = gw;
+    a.gh = gh;
+    a.k = kk;
+    std::vector<uint8_t> lab(np), smp;   // (smp: host Dinic only)
+    std::vector<uint16_t> cov(np);
+    static const char what[] = "seam finding";
+    mcs::Scratch sc(A, p->stream);
+    HIP_TRY_AS(what, sc.dev(&a.label, np));
+    HIP_TRY_AS(what, sc.dev(&a.cov, np));
+    HIP_TRY_AS(what, sc.dev(&a.samples, np * C * n));
+    HIP_TRY_AS(what, A->hipMemsetAsync(a.samples, 0, np * C * n, p->stream));
+    rc = launch_args(A, k->seam_sample[C][p->fd.interp], (unsigned)((np + 255) / 256), 1, 256, 1,
+                     &a, sizeof(a), p->stream);
+    if (rc) return rc;
+    // the pairwise cuts: push-relabel on the device (default), or the host Dinic
+    // (MCS_SEAM_FLOW=host; the checker of the device path)
+    static const bool host_flow =
+        getenv("MCS_SEAM_FLOW") && !strcmp(getenv("MCS_SEAM_FLOW"), "host");
+    HIP_TRY_AS(what, A->hipMemcpyAsync(cov.data(), a.cov, np * 2, hipMemcpyDeviceToHost,
+                                       p->stream));
+    if (host_flow) {
+        HIP_TRY_AS(what, A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost,
+                                           p->stream));
+        smp.resize(np * C * n);
+        HIP_TRY_AS(what, A->hipMemcpyAsync(smp.data(), a.samples, np * C * n,
+                                           hipMemcpyDeviceToHost, p->stream));
+    }
+    HIP_TRY_AS(what, sc.sync());
+    if (host_flow) {
+        rc = mcs::seam_graphcut(n, gw, gh, lab.data(), cov.data(), smp.data(), C);
+        if (rc) return rc;
+        HIP_TRY_AS(what, A->hipMemcpyAsync(a.label, lab.data(), np, hipMemcpyHostToDevice,
+                                           p->stream));
+    } else {
+        rc = mcs::seam_graphcut_device(p->device, p->stream, n, gw, gh, a.label, a.cov, a.samples,
+                                       C, cov.data(), p->seam_stats);
+        if (rc) return rc;
+        HIP_TRY_AS(what, A->hipMemcpyAsync(lab.data(), a.label, np, hipMemcpyDeviceToHost,
+                                           p->stream));
+    }
+    HIP_TRY_AS(what, sc.sync());
+    p->d_seam = sc.keep(a.label);   // the device labels (the seam grid the stitch kernels read)
+    p->seam_lab.swap(lab);
+    p->seam_w = gw;
+    p->seam_h = gh;
+    p->seam_k = kk;
+    p->kp.seam_hint = p->d_seam;
+    p->kp.seam_w = gw;
+    p->kp.seam_shift = kk;
+    return MCS_OK;
+}
+
+int mcs_seam_graphcut_host(int n_cams, int gw, int gh, uint8_t *labels, const uint16_t *cover,
+                           const uint8_t *samples, int channels)
+{
+    mcs::clear_error();
+    if (!labels || !cover || !samples) return mcs::fail(MCS_E_INVALID, "NULL input");
+    if (n_cams < 1 || n_cams > 16 || gw < 1 || gh < 1 || channels < 1 || channels > 4 ||
+        (int64_t)gw * gh > (int64_t)1 << 28)
+        return mcs::fail(MCS_E_INVALID, "n_cams %d, grid %dx%d, channels %d", n_cams, gw, gh,
+                         channels);
+    return mcs::seam_graphcut(n_cams, gw, gh, labels, cover, samples, channels);
+}
+
+// mcs_seam_graphcut_device on its stream s, after the checks.
+static int graphcut_on_stream(const Api *A, hipStream_t s, int n_cams, int gw, int gh,
+                              uint8_t *labels, const uint16_t *cover, const uint8_t *samples,
+                              int channels, int device, int64_t *stats)
+{
+    static const char what[] = "seam graph cut";
+    const size_t np = (size_t)gw * gh, sb = np * n_cams * channels;
+    mcs::Scratch sc(A, s);
+    uint8_t *buf = nullptr;
+    HIP_TRY_AS(what, sc.dev(&buf, np * 3 + sb + 16));
+    uint8_t *d_lab = buf, *d_smp = buf + np * 3 + 16;
+    uint16_t *d_cov = reinterpret_cast<uint16_t *>(buf + ((np + 7) & ~(size_t)7));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_lab, labels, np, hipMemcpyHostToDevice, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_cov, cover, np * 2, hipMemcpyHostToDevice, s));
+    HIP_TRY_AS(what, A->hipMemcpyAsync(d_smp, samples, sb, hipMemcpyHostToDevice, s));
+    const int rc = mcs::seam_graphcut_device(device, s, n_cams, gw, gh, d_lab, d_cov, d_smp,
+                                             channels, cover, stats);
+    if (rc) return rc;
+    HIP_TRY_AS(what, A->hipMemcpyAsync(labels, d_lab, np, hipMemcpyDeviceToHost, s));
+    HIP_TRY_AS(what, sc.sync());
+    // (this entry point has always synchronised twice here: the runtime sees the calls it saw)
+    HIP_TRY_AS(what, sc.sync());
+    return MCS_OK;
+}
+
+int mcs_seam_graphcut_device(int n_cams, int gw, int gh, uint8_t *labels, const uint16_t *cover,
+                             const uint8_t *samples, int channels, int device, int64_t *stats)
+{
+    mcs::clear_error();
+    if (!labels || !cover || !samples) return mcs::fail(MCS_E_INVALID, "NULL input");
+    if (n_cams < 1 || n_cams > 16 || gw < 1 || gh < 1 || channels < 1 || channels > 4 ||
+        (int64_t)gw * gh > (int64_t)1 << 28)
+        return mcs::fail(MCS_E_INVALID, "n_cams %d, grid %dx%d, channels %d", n_cams, gw, gh,
+                         channels);
+    const mcs::Entry A(device);
+    if (A.status) return A.status;
+    hipStream_t s = nullptr;
+    HIP_TRY(A->hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    const int rc = graphcut_on_stream(A, s, n_cams, gw, gh, labels, cover, samples, channels,
+                                      device, stats);
+    (void)A->hipStreamDestroy(s);
+    return rc;
+}
+
+int mcs_plan_seam_stats(const mcs_plan *p, int64_t *stats)
+{
+    if (!p || !stats) return mcs::fail(MCS_E_INVALID, "NULL plan/stats");
+    for (int j = 0; j < 5; j++) stats[j] = p->seam_stats[j];
+    return MCS_OK;
+}
+
+int mcs_plan_seam_labels(const mcs_plan *p, uint8_t *out, int *w, int *h)
+{
+    if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
+    if (w) *w = p->seam_w;
+    if (h) *h = p->seam_h;
+    if (out && !p->seam_lab.empty()) memcpy(out, p->seam_lab.data(), p->seam_lab.size());
+    return MCS_OK;
+}
+
+}  // extern "C"

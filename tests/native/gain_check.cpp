@@ -27,7 +27,8 @@ static int launches()
     return n;
 }
 
-// what the linked sources need of mcs_capi.cpp
+// what the linked sources need of mcs_capi.cpp: the plan's stream and host-path buffers (their
+// other callers, mcs_stitch.cpp and mcs_seam.cpp, are not linked either)
 int mcs::host::ensure_stream(const Api *, mcs_plan *) { return MCS_OK; }
 int mcs::host::ensure_host_buffers(const Api *, mcs_plan *p)
 {

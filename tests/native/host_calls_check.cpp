@@ -9,9 +9,14 @@
 // 64 x 48 frame (the one-launch pyramid, the resize chain, one level, and a device ranking
 // "overflow" that sends the call through host ranking); `rig`, rig jobs on the device path -- a
 // 3-camera job captured as a graph, replayed, and re-captured after mcs_rig_job_set_lens, then a
-// 2-capture batch job whose 2x pyramid takes plain launches.  The rig job's overflow fallback is
-// left out of the injection: it runs the per-call steps on pool threads, whose thread-lifetime
-// workspaces make the allocation snapshots depend on which thread ran what.  Per scenario:
+// 2-capture batch job whose 2x pyramid takes plain launches.  One on the entry points that render
+// a mosaic: `stitch`, the host-array stitch and the six device forms (prepared, direct and direct
+// multi-band, each with its _gained twin) over 3 captures, on every plan in its blend modes, with
+// frames back to back and with a stride of its own per camera, without gains and with a gain on
+// a used camera (the forms without _gained must refuse such a plan).  The rig job's overflow
+// fallback is left out of the injection: it runs the per-call steps on pool threads, whose
+// thread-lifetime workspaces make the allocation snapshots depend on which thread ran what.  Per
+// scenario:
 //   (a) a clean run, its log printed one event a line;
 //   (b) for k = 1 .. the clean run's runtime calls: call k fails.  The scenario returns a non-zero
 //       status; once the plans are destroyed, the device allocations, streams and pinned
@@ -312,6 +317,77 @@ static int run_rig()
     return rc;
 }
 
+// Three captures through the device entry points that take the plan's blend mode: the prepared
+// path and the table-free one (mcs_stitch_direct, or the multi-band form with a work area of the
+// size it asks for: a fake pointer, as the frames and the mosaic are).  strides: NULL (frames
+// back to back, one launch chain per batch) or one stride per camera, no two alike (a chain per
+// capture: the only case in which the walk's pointer arithmetic reaches the argument blocks).
+// gains: the plan has gains on a used camera -- the forms without _gained must refuse it.
+static int stitch_batch(mcs_plan *p, int mode, const int64_t *strides, bool gains)
+{
+    int w = 0, h = 0, c = 0;
+    mcs_plan_out_shape(p, &w, &h, &c);
+    uint8_t *const out = (uint8_t *)(uintptr_t)0x8000000;
+    void *const work = (void *)(uintptr_t)0x5000000;
+    const int64_t pitch = (int64_t)w * c, ofs = strides ? pitch * h + 64 : 0;
+    int64_t wb = -1;
+    CHECK(mcs_direct_multiband_work_size(p, &wb) == MCS_OK && wb >= 4);
+    const bool mb = mode == MCS_BLEND_MULTIBAND;
+    int rc = MCS_OK;
+    if (gains) {
+        CHECK(mcs_stitch_device(p, DEV_CAMS, strides, out, pitch, ofs, 3, g_stream) ==
+              MCS_E_UNSUPPORTED);
+        CHECK((mb ? mcs_stitch_direct_multiband(p, DEV_CAMS, strides, out, pitch, ofs, 3, work, wb,
+                                                g_stream)
+                  : mcs_stitch_direct(p, DEV_CAMS, strides, out, pitch, ofs, 3, g_stream)) ==
+              MCS_E_UNSUPPORTED);
+    } else {
+        rc = mcs_stitch_device(p, DEV_CAMS, strides, out, pitch, ofs, 3, g_stream);
+        if (rc == MCS_OK)
+            rc = mb ? mcs_stitch_direct_multiband(p, DEV_CAMS, strides, out, pitch, ofs, 3, work,
+                                                  wb, g_stream)
+                    : mcs_stitch_direct(p, DEV_CAMS, strides, out, pitch, ofs, 3, g_stream);
+    }
+    if (rc == MCS_OK)
+        rc = mcs_stitch_device_gained(p, DEV_CAMS, strides, out, pitch, ofs, 3, g_stream);
+    if (rc == MCS_OK)
+        rc = mb ? mcs_stitch_direct_multiband_gained(p, DEV_CAMS, strides, out, pitch, ofs, 3, work,
+                                                     wb, g_stream)
+                : mcs_stitch_direct_gained(p, DEV_CAMS, strides, out, pitch, ofs, 3, g_stream);
+    return rc;
+}
+
+// The chain in its four blend modes, the cylinder and the 1 x 1 mosaic in two of theirs (a
+// cylinder has no paste order).  Per mode: the host-array stitch, then stitch_batch with both
+// kinds of strides, all of it once without gains and once with a gain on camera 1.
+static int run_stitch()
+{
+    Plans P;
+    make_plans(P);
+    static const int modes[3][4] = {
+        {MCS_BLEND_NONE, MCS_BLEND_SEAM, MCS_BLEND_FEATHER, MCS_BLEND_MULTIBAND},
+        {MCS_BLEND_FEATHER, MCS_BLEND_MULTIBAND, -1, -1},
+        {MCS_BLEND_SEAM, MCS_BLEND_MULTIBAND, -1, -1}};
+    const int64_t strides[3] = {0x10000, 0x10100, 0x10200};
+    const double gains[3] = {1.0, 1.5, 1.0};
+    std::vector<uint8_t> mosaic(256 * 64 * 3);    // (larger than any mosaic)
+    int rc = MCS_OK;
+    for (int i = 0; i < 3 && rc == MCS_OK; i++)
+        for (int m = 0; m < 4 && modes[i][m] >= 0 && rc == MCS_OK; m++) {
+            mcs_plan *p = P.p[i];
+            rc = mcs_plan_set_blend(p, modes[i][m]);
+            for (int g = 0; g < 2 && rc == MCS_OK; g++) {
+                CHECK(mcs_plan_set_gains(p, g ? gains : nullptr) == MCS_OK);
+                rc = mcs_stitch_host(p, HOST_CAMS, mosaic.data());
+                if (rc == MCS_OK) rc = stitch_batch(p, modes[i][m], nullptr, g);
+                if (rc == MCS_OK) rc = stitch_batch(p, modes[i][m], strides, g);
+            }
+            CHECK(mcs_plan_set_gains(p, nullptr) == MCS_OK);
+        }
+    destroy_plans(P);
+    return rc;
+}
+
 struct Snapshot {
     size_t live, pinned, streams, events, graphs, execs;
     int bad_free;
@@ -410,6 +486,11 @@ int main(int argc, char **argv)
     scenario("orb", run_orb, 0);
     // (the jobs are released after the injected part, as the plans are)
     scenario("rig", run_rig, 0);
+    // mcs_plan_set_blend on a prepared plan begins with release_tables, which drains the plan's own
+    // stream (the host-array stitch made it; on the stub no plan comes to side streams): the
+    // chain's three changes of mode, and the second mode of the cylinder and of the 1 x 1 mosaic
+    // (their first is set before anything was prepared)
+    scenario("stitch", run_stitch, 5);
     if (g_bad == 0) printf("ok\n");
     return g_bad ? 1 : 0;
 }

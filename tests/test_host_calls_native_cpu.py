@@ -20,7 +20,7 @@ CSRC = os.path.join(ROOT, "multicamera_stitching_amd", "csrc")
 # every host source but the two the stub stands in for (the runtime binding, the module loader)
 HOST = [s for s in build.HOST_SRC if s not in ("hip_rt.cpp", "mcs_runtime.cpp")]
 PROGRAMS = {"scratch_check": [], "host_calls_check": HOST}
-SCENARIOS = ("seams", "footprint", "graphcut", "overlap", "match", "orb", "rig")
+SCENARIOS = ("seams", "footprint", "graphcut", "overlap", "match", "orb", "rig", "stitch")
 
 
 def run_program(tmp_path, name, flags):
