@@ -178,6 +178,28 @@ int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const dou
  * mcs_lens_map_host. */
 int mcs_lens_unmap_host(const double *K, const double *dist, int n_dist, const double *xy, int n,
                         double *uv);
+/* Lens models.  MCS_LENS_PINHOLE: cv::initUndistortRectifyMap's rational polynomial, the model of
+ * the four entry points above, which are these with model MCS_LENS_PINHOLE.  MCS_LENS_FISHEYE:
+ * cv2.fisheye.initUndistortRectifyMap with R = I and P = K, the equidistant model
+ * theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) of the ray's angle
+ * theta = atan(r), evaluated per position with an arctangent of the library's own (+ - * / in a
+ * fixed FP64 order: host and device agree bit for bit).  dist is k1..k4 (n_dist 4) or absent
+ * (n_dist 0, all zero); any other count: MCS_E_UNSUPPORTED.  K as for the polynomial model.
+ * Valid angle: the first theta = i / 1024, i = 1..1608, at which theta_d is not positive or stops
+ * growing, one step back (+inf when there is none); a position whose angle is beyond it, or
+ * whose radius is not finite, is outside the lens.  The inverse is radial: 10 Newton steps on
+ * theta_d(atan(r)) from r = theta_d, accepted as mcs_lens_unmap_host accepts.  An unknown model:
+ * MCS_E_INVALID.  A rig may mix cameras of both models and cameras without a lens.
+ * mcs_lens_map_host_model: *limit (optional) receives r2max for MCS_LENS_PINHOLE and the valid
+ * angle for MCS_LENS_FISHEYE. */
+#define MCS_LENS_PINHOLE 0
+#define MCS_LENS_FISHEYE 1
+int mcs_plan_set_lens_model(mcs_plan *plan, int cam, int model, const double *K,
+                            const double *dist, int n_dist);
+int mcs_lens_map_host_model(int model, const double *K, const double *dist, int n_dist,
+                            const double *uv, int n, double *xy, double *limit);
+int mcs_lens_unmap_host_model(int model, const double *K, const double *dist, int n_dist,
+                              const double *xy, int n, double *uv);
 int mcs_plan_destroy(mcs_plan *plan);
 int mcs_plan_out_shape(const mcs_plan *plan, int *w, int *h, int *channels);
 int mcs_plan_describe(const mcs_plan *plan, mcs_flat_desc *out);
@@ -628,6 +650,9 @@ int mcs_rig_job_gains(const mcs_rig_job *job, double *gains, uint16_t *q, int *e
  * graph (the next capture records the chain again); touches no device itself. */
 int mcs_rig_job_set_lens(mcs_rig_job *job, int cam, const double *K, const double *dist,
                          int n_dist);
+/* The same with a lens model (MCS_LENS_*, see mcs_plan_set_lens_model). */
+int mcs_rig_job_set_lens_model(mcs_rig_job *job, int cam, int model, const double *K,
+                               const double *dist, int n_dist);
 /* Captures the job finished on the device path (one launch chain) and on the per-call path (a
  * device ranking overflow, or MCS_RIG_PATH=calls). */
 int mcs_rig_job_counts(const mcs_rig_job *job, int *device_captures, int *call_captures);

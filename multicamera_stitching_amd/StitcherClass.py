@@ -274,13 +274,16 @@ class Stitcher(_Transient, Debugger):
         return _get_plan(self, self.stitchers, cam0, channels, interp, device)
 
     def set_lenses(self, lenses):
-        """Cameras that deliver RAW frames (extension): {label: (K, dist) or None}.
+        """Cameras that deliver RAW frames (extension): {label: (K, dist), (K, dist, "fisheye")
+        or None}.
 
         K is the 3x3 camera matrix at the camera's calibrated size and dist its OpenCV distortion
         vector, as the caller would pass them to cv2.undistort before ``stitch``.  With a lens
         set, ``stitch`` takes that camera's frames as the sensor delivers them: the undistortion
         is part of the plan's own map (mcs_plan_set_lens), one resampling instead of two and no
-        undistorted copy.  None (or a missing label) removes a camera's lens; ``set_lenses({})``
+        undistorted copy.  (K, D, "fisheye"): a cv2.fisheye calibration (K, D of four
+        coefficients), mapped as cv2.fisheye.initUndistortRectifyMap with R = I and P = K does;
+        a rig may mix both models.  None (or a missing label) removes a camera's lens; ``set_lenses({})``
         removes all.  Not pickled: a loaded stitcher has no lenses until they are set again.
         """
         labels = [str(l) for l in self.img_labels]
@@ -290,10 +293,11 @@ class Stitcher(_Transient, Debugger):
                 raise KeyError("no camera labelled {!r}".format(label))
             if lens is None:
                 continue
-            K, dist = lens
+            K, dist = lens[:2]
+            model = _capi.lens_model(lens[2]) if len(lens) > 2 else _capi.MCS_LENS_PINHOLE
             k = np.array(K, dtype=np.float64).reshape(3, 3)
             d = np.array([] if dist is None else dist, dtype=np.float64).reshape(-1)
-            table[labels.index(str(label))] = (k, d)
+            table[labels.index(str(label))] = (k, d, model)
         if table:
             self.__dict__["_mcs_lenses"] = table
         else:
@@ -471,15 +475,15 @@ def _get_plan(owner, chain, cam0_shape, channels, interp=None, device=None):
     # Stitcher.set_lenses: camera index (sorted-label order) -> (K, dist)
     lenses = owner.__dict__.get("_mcs_lenses") or {}
     if lenses:
-        key += (tuple((i, k.tobytes(), d.tobytes()) for i, (k, d) in sorted(lenses.items())),)
+        key += (tuple((i, k.tobytes(), d.tobytes(), m) for i, (k, d, m) in sorted(lenses.items())),)
     cache = owner._cache()
 
     def make():
         plan = _capi.Plan(descs, cam0_shape[1], cam0_shape[0], channels, interp, device)
         if blend != _capi.MCS_BLEND_NONE:
             plan.set_blend(blend)
-        for i, (k, d) in sorted(lenses.items()):
-            plan.set_lens(i, k, d)
+        for i, (k, d, m) in sorted(lenses.items()):
+            plan.set_lens(i, k, d, m)
         return plan
     plan = cache.get(key, make)
     # Stitcher.set_gains: host-side state of the plan (no table depends on it), so it is not

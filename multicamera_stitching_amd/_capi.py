@@ -57,6 +57,8 @@ EXPORTS = (
     "mcs_rig_job_set_blend", "mcs_plan_overlap_stats_direct",
     "mcs_plan_overlap_stats_direct_async", "mcs_rig_job_set_exposure", "mcs_rig_job_gains",
     "mcs_lens_unmap_host", "mcs_rig_job_set_lens",
+    "mcs_plan_set_lens_model", "mcs_rig_job_set_lens_model", "mcs_lens_map_host_model",
+    "mcs_lens_unmap_host_model",
     "mcs_direct_multiband_work_size", "mcs_stitch_direct_multiband",
     "mcs_stitch_direct_multiband_gained", "mcs_rig_job_set_multiband",
 )
@@ -300,6 +302,14 @@ def load() -> ctypes.CDLL:
         L.mcs_lens_unmap_host.restype = I
         L.mcs_rig_job_set_lens.argtypes = [P, I, P, P, I]
         L.mcs_rig_job_set_lens.restype = I
+        L.mcs_plan_set_lens_model.argtypes = [P, I, I, P, P, I]
+        L.mcs_plan_set_lens_model.restype = I
+        L.mcs_rig_job_set_lens_model.argtypes = [P, I, I, P, P, I]
+        L.mcs_rig_job_set_lens_model.restype = I
+        L.mcs_lens_map_host_model.argtypes = [I, P, P, I, P, I, P, P]
+        L.mcs_lens_map_host_model.restype = I
+        L.mcs_lens_unmap_host_model.argtypes = [I, P, P, I, P, I, P]
+        L.mcs_lens_unmap_host_model.restype = I
         L.mcs_match_l2_knn2.argtypes = [P, I, P, I, I, P, P, P, I, P]
         L.mcs_match_l2_knn2.restype = I
         L.mcs_match_l2_knn2_host.argtypes = [P, I, P, I, I, P, P, P, I]
@@ -669,16 +679,18 @@ class Plan:
         check(self._lib.mcs_plan_set_blend(self._h, int(mode)))
         return self
 
-    def set_lens(self, cam: int, K, dist=None):
-        """mcs_plan_set_lens: camera `cam` (sorted-label order) delivers RAW frames, undistorted
-        inside the plan's own map by the lens (K, dist); K=None removes the lens."""
+    def set_lens(self, cam: int, K, dist=None, model="pinhole"):
+        """mcs_plan_set_lens_model: camera `cam` (sorted-label order) delivers RAW frames,
+        undistorted inside the plan's own map by the lens (K, dist) of `model` ("pinhole": the
+        OpenCV polynomial, "fisheye": cv2.fisheye's, or an MCS_LENS_* value); K=None removes
+        the lens."""
         if K is None:
             check(self._lib.mcs_plan_set_lens(self._h, int(cam), None, None, 0))
             return self
         k, d = _lens_args(K, dist)
-        check(self._lib.mcs_plan_set_lens(self._h, int(cam), k.ctypes.data_as(ctypes.c_void_p),
-                                          d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
-                                          int(d.size)))
+        check(self._lib.mcs_plan_set_lens_model(
+            self._h, int(cam), lens_model(model), k.ctypes.data_as(ctypes.c_void_p),
+            d.ctypes.data_as(ctypes.c_void_p) if d.size else None, int(d.size)))
         return self
 
     def overlap_stats(self, cam_ptrs, cam_frame_strides, n_frames: int, step_log2: int = 2,
@@ -1169,17 +1181,18 @@ class RigJob:
         check(self._lib.mcs_rig_job_set_exposure(self._h, int(step_log2), float(alpha),
                                                  float(beta)))
 
-    def set_lens(self, cam: int, K, dist=None):
-        """mcs_rig_job_set_lens: camera `cam` delivers RAW frames; its matched keypoints go
+    def set_lens(self, cam: int, K, dist=None, model="pinhole"):
+        """mcs_rig_job_set_lens_model: camera `cam` delivers RAW frames; its matched keypoints go
         through the inverse lens before the pair homographies are estimated, and wait_stitch
-        sets the lens on the capture's plan.  K=None removes the lens.  Between captures only."""
+        sets the lens on the capture's plan.  model as Plan.set_lens.  K=None removes the lens.
+        Between captures only."""
         if K is None:
             check(self._lib.mcs_rig_job_set_lens(self._h, int(cam), None, None, 0))
             return self
         k, d = _lens_args(K, dist)
-        check(self._lib.mcs_rig_job_set_lens(self._h, int(cam), k.ctypes.data_as(ctypes.c_void_p),
-                                             d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
-                                             int(d.size)))
+        check(self._lib.mcs_rig_job_set_lens_model(
+            self._h, int(cam), lens_model(model), k.ctypes.data_as(ctypes.c_void_p),
+            d.ctypes.data_as(ctypes.c_void_p) if d.size else None, int(d.size)))
         return self
 
     def gains(self):
@@ -1278,9 +1291,23 @@ def _lens_args(K, dist):
     return k, d
 
 
-def lens_map_host(K, dist, uv, with_r2max: bool = False):
-    """mcs_lens_map_host: positions uv (..., 2) of the undistorted image -> positions in the raw
-    frame (same shape, float64; NaN beyond the valid radius), optionally with r2max."""
+MCS_LENS_PINHOLE, MCS_LENS_FISHEYE = 0, 1
+_LENS_MODELS = {"pinhole": MCS_LENS_PINHOLE, "fisheye": MCS_LENS_FISHEYE}
+
+
+def lens_model(model) -> int:
+    """"pinhole" / "fisheye" (or an integer, passed on as it is) -> MCS_LENS_*."""
+    if isinstance(model, str):
+        if model not in _LENS_MODELS:
+            raise ValueError("lens model {!r} (pinhole or fisheye)".format(model))
+        return _LENS_MODELS[model]
+    return int(model)
+
+
+def lens_map_host(K, dist, uv, with_r2max: bool = False, model="pinhole"):
+    """mcs_lens_map_host_model: positions uv (..., 2) of the undistorted image -> positions in
+    the raw frame (same shape, float64; NaN beyond the valid radius / angle), optionally with
+    the limit (r2max; fisheye: tmax)."""
     L = load()
     k, d = _lens_args(K, dist)
     pts = np.ascontiguousarray(np.asarray(uv, np.float64))
@@ -1288,15 +1315,16 @@ def lens_map_host(K, dist, uv, with_r2max: bool = False):
         raise ValueError("uv must have shape (..., 2)")
     out = np.empty_like(pts)
     r2 = ctypes.c_double(0.0)
-    check(L.mcs_lens_map_host(k.ctypes.data_as(ctypes.c_void_p),
-                              d.ctypes.data_as(ctypes.c_void_p) if d.size else None, int(d.size),
-                              pts.ctypes.data_as(ctypes.c_void_p), int(pts.size // 2),
-                              out.ctypes.data_as(ctypes.c_void_p), ctypes.byref(r2)))
+    check(L.mcs_lens_map_host_model(lens_model(model), k.ctypes.data_as(ctypes.c_void_p),
+                                    d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
+                                    int(d.size), pts.ctypes.data_as(ctypes.c_void_p),
+                                    int(pts.size // 2), out.ctypes.data_as(ctypes.c_void_p),
+                                    ctypes.byref(r2)))
     return (out, r2.value) if with_r2max else out
 
 
-def lens_unmap_host(K, dist, xy):
-    """mcs_lens_unmap_host: raw-frame positions xy (..., 2) -> positions in the undistorted image
+def lens_unmap_host(K, dist, xy, model="pinhole"):
+    """mcs_lens_unmap_host_model: raw-frame positions xy (..., 2) -> positions in the undistorted image
     (same shape, float64; NaN, NaN where the lens has no valid inverse)."""
     L = load()
     k, d = _lens_args(K, dist)
@@ -1304,10 +1332,10 @@ def lens_unmap_host(K, dist, xy):
     if pts.shape[-1:] != (2,):
         raise ValueError("xy must have shape (..., 2)")
     out = np.empty_like(pts)
-    check(L.mcs_lens_unmap_host(k.ctypes.data_as(ctypes.c_void_p),
-                                d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
-                                int(d.size), pts.ctypes.data_as(ctypes.c_void_p),
-                                int(pts.size // 2), out.ctypes.data_as(ctypes.c_void_p)))
+    check(L.mcs_lens_unmap_host_model(lens_model(model), k.ctypes.data_as(ctypes.c_void_p),
+                                      d.ctypes.data_as(ctypes.c_void_p) if d.size else None,
+                                      int(d.size), pts.ctypes.data_as(ctypes.c_void_p),
+                                      int(pts.size // 2), out.ctypes.data_as(ctypes.c_void_p)))
     return out
 
 

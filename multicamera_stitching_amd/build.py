@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import hashlib
 import os
+from concurrent.futures import ThreadPoolExecutor
 import struct
 import subprocess
 import sys
@@ -27,6 +28,11 @@ ARCH = os.environ.get("MCS_OFFLOAD_ARCH", "gfx950")
 # device sources -> embedded code objects (blob symbol mcs_hsaco_<name>_start)
 DEVICE = {"stitch": "mcs_kernels.hip", "features": "mcs_features.hip", "sweep": "mcs_sweep.hip",
           "direct_mb": "mcs_direct_mb.hip"}
+# The sources whose kernels map through a plan's lenses are built twice: as above with the
+# polynomial lens model alone (MCS_LENS_MODELS=0, mcs_lens_core.h: the registers of a plan
+# without a fisheye camera stay where they were), and as <name>_fish with the model read per
+# camera, for the plans that have one (csrc/mcs_prepare.cpp kernels()).
+FISH = ("stitch", "sweep", "direct_mb")
 # the code objects mcs_build_id names: the code bench.py times and the counter records attach to
 # (the direct multi-band object is loaded beside them and kept out of the id)
 ID_OBJECTS = ("features", "stitch", "sweep")
@@ -135,13 +141,20 @@ def _fresh(out: str, src: str) -> bool:
 
 def _build_to(LIB: str, HSACO: str, defines, verbose: bool) -> str:
     objs = {}
-    for name, src in DEVICE.items():
+    jobs = []
+    for name, src in [*DEVICE.items(), *[(n + "_fish", DEVICE[n]) for n in FISH]]:
         out = HSACO if name == "stitch" else HSACO.replace("mcs_kernels", "mcs_" + name)
         if defines or not _fresh(out, src):
-            _run([HIPCC, *DEVICE_FLAGS, *["-D" + d for d in defines], *INC, "-o", out + ".tmp",
-                  os.path.join(CSRC, src)], verbose)
-            os.replace(out + ".tmp", out)
+            models = [] if name.endswith("_fish") or name == "features" else ["-DMCS_LENS_MODELS=0"]
+            jobs.append(([HIPCC, *DEVICE_FLAGS, *models, *["-D" + d for d in defines], *INC,
+                          "-o", out + ".tmp", os.path.join(CSRC, src)], out))
         objs[name] = out
+    # the device compiles are independent: run them side by side
+    with ThreadPoolExecutor(max(1, min(len(jobs), os.cpu_count() or 1, 8))) as pool:
+        for _ in pool.map(lambda j: _run(j[0], verbose), jobs):
+            pass
+    for _, out in jobs:
+        os.replace(out + ".tmp", out)
     build_id = code_id([objs[name] for name in ID_OBJECTS])
     blob = LIB + ".blob.S"
     with open(blob, "w") as f:

@@ -345,7 +345,7 @@ int mcs_stitch_host_sized(mcs_plan *p, const uint8_t *const *cams, const int *ca
     if (rc) return rc;
     if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
     const Kernels *k = nullptr;
-    rc = kernels(A, p->device, &k);
+    rc = kernels(A, p, &k);
     if (rc) return rc;
     // only cameras that contribute are uploaded (a passthrough stage's A is never read); a frame
     // off its calibrated size is resized on the device first (StitcherClass.py:226-233)
@@ -471,6 +471,12 @@ int mcs_plan_set_blend(mcs_plan *p, int mode)
 
 int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist, int n_dist)
 {
+    return mcs_plan_set_lens_model(p, cam, MCS_LENS_PINHOLE, K, dist, n_dist);
+}
+
+int mcs_plan_set_lens_model(mcs_plan *p, int cam, int model, const double *K, const double *dist,
+                            int n_dist)
+{
     mcs::clear_error();
     if (!p) return mcs::fail(MCS_E_INVALID, "NULL plan");
     if (!p->map_tab.empty())
@@ -480,7 +486,7 @@ int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist,
     mcs::Lens L;
     if (K) {
         if (n_dist < 0 || (n_dist > 0 && !dist)) return mcs::fail(MCS_E_INVALID, "NULL dist");
-        const int rc = mcs::lens_from(K, dist, n_dist, &L);
+        const int rc = mcs::lens_from(K, dist, n_dist, &L, model);
         if (rc) return rc;
     } else if (!((p->kp.lens_mask >> cam) & 1u)) {
         return MCS_OK;   // none to remove
@@ -495,9 +501,11 @@ int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist,
     if (K) {
         p->lens[cam] = L;
         p->kp.lens_mask |= 1u << cam;
+        p->fish_mask = (p->fish_mask & ~(1u << cam)) | (model == MCS_LENS_FISHEYE ? 1u << cam : 0u);
     } else {
         p->lens[cam] = mcs::Lens();
         p->kp.lens_mask &= ~(1u << cam);
+        p->fish_mask &= ~(1u << cam);
     }
     p->lens_stale = true;
     return MCS_OK;
@@ -506,11 +514,17 @@ int mcs_plan_set_lens(mcs_plan *p, int cam, const double *K, const double *dist,
 int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const double *uv, int n,
                       double *xy, double *r2max)
 {
+    return mcs_lens_map_host_model(MCS_LENS_PINHOLE, K, dist, n_dist, uv, n, xy, r2max);
+}
+
+int mcs_lens_map_host_model(int model, const double *K, const double *dist, int n_dist,
+                            const double *uv, int n, double *xy, double *r2max)
+{
     mcs::clear_error();
     if (!K || (n_dist > 0 && !dist) || n < 0 || (n > 0 && (!uv || !xy)))
         return mcs::fail(MCS_E_INVALID, "NULL K/dist/uv/xy");
     mcs::Lens L;
-    const int rc = mcs::lens_from(K, dist, n_dist < 0 ? 0 : n_dist, &L);
+    const int rc = mcs::lens_from(K, dist, n_dist < 0 ? 0 : n_dist, &L, model);
     if (rc) return rc;
     if (r2max) *r2max = L.r2max;
     for (int i = 0; i < n; i++) {
@@ -525,11 +539,17 @@ int mcs_lens_map_host(const double *K, const double *dist, int n_dist, const dou
 int mcs_lens_unmap_host(const double *K, const double *dist, int n_dist, const double *xy, int n,
                         double *uv)
 {
+    return mcs_lens_unmap_host_model(MCS_LENS_PINHOLE, K, dist, n_dist, xy, n, uv);
+}
+
+int mcs_lens_unmap_host_model(int model, const double *K, const double *dist, int n_dist,
+                              const double *xy, int n, double *uv)
+{
     mcs::clear_error();
     if (!K || (n_dist > 0 && !dist) || n < 0 || (n > 0 && (!xy || !uv)))
         return mcs::fail(MCS_E_INVALID, "NULL K/dist/xy/uv");
     mcs::Lens L;
-    const int rc = mcs::lens_from(K, dist, n_dist < 0 ? 0 : n_dist, &L);
+    const int rc = mcs::lens_from(K, dist, n_dist < 0 ? 0 : n_dist, &L, model);
     if (rc) return rc;
     for (int i = 0; i < n; i++) {
         double u = std::nan(""), v = std::nan("");
@@ -569,7 +589,7 @@ int mcs_plan_footprint(mcs_plan *p, int64_t *touched_px, int n_cams)
     int rc = ensure_stream(A, p);
     if (rc) return rc;
     const Kernels *k = nullptr;
-    rc = kernels(A, p->device, &k);
+    rc = kernels(A, p, &k);
     if (rc) return rc;
     rc = upload_plan_tables(A, p, p->stream);
     if (rc) return rc;

@@ -31,20 +31,28 @@ int build_flat(const mcs_stage_desc *stages, int n_stages, int cam0_w, int cam0_
 void fill_kparams(const mcs_flat_desc &fd, KParams *kp);
 int block_width(int W, int H);
 bool undistort_map(const double *K, const double *dist, int n_dist, int w, int h, int32_t *tab);
-// Lens (mcs_lens_core.h) of a camera matrix and an OpenCV distortion vector, r2max included;
-// MCS_E_UNSUPPORTED / MCS_E_INVALID for what the model does not cover.
-int lens_from(const double *K, const double *dist, int n_dist, Lens *L);
+// Lens (mcs_lens_core.h) of a camera matrix and an OpenCV distortion vector (model
+// MCS_LENS_PINHOLE) or a cv2.fisheye one (MCS_LENS_FISHEYE: 0 or 4 coefficients), r2max / tmax
+// included; MCS_E_UNSUPPORTED / MCS_E_INVALID for what the model does not cover.
+int lens_from(const double *K, const double *dist, int n_dist, Lens *L,
+              int model = MCS_LENS_PINHOLE);
 // Pairwise graph-cut seam labels over the seam grid (mcs_seam.cpp; spec: oracle/orc_seam.c).
 int seam_graphcut(int n_cams, int gw, int gh, uint8_t *lab, const uint16_t *cov,
                   const uint8_t *smp, int cn);
 
-// Embedded gfx950 code objects (one per device source, see build.py) and their kernels.
+// Embedded gfx950 code objects (one per device source, see build.py) and their kernels.  The
+// stitch, sweep and direct multi-band sources are built twice: the first build maps lenses by the
+// polynomial model only (MCS_LENS_MODELS=0: the code a plan without a fisheye camera runs), the
+// *Fish build reads the model of every lens row.
 enum Module {
     kModStitch = 0,
     kModFeatures = 1,
     kModSweep = 2,
     kModDirectMb = 3,
-    kNumModules = 4
+    kModStitchFish = 4,
+    kModSweepFish = 5,
+    kModDirectMbFish = 6,
+    kNumModules = 7
 };
 constexpr int kMaxDevices = 64;
 // Loads module `m` on `device` once (the device must be current) and looks up `name`.

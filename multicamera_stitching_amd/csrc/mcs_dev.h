@@ -77,6 +77,7 @@ __device__ __forceinline__ Lens lens_row(const KParams &P, int cam)
 #pragma unroll
     for (int i = 0; i < 12; i++) L.k[i] = t[4 + i];
     L.r2max = t[16];
+    L.model = MCS_LENS_MODELS ? t[17] : 0.0;
     return L;
 }
 

@@ -139,7 +139,7 @@ int enqueue_direct_stats(const Api *A, mcs_plan *p, const uint8_t *const *d_cams
     HIP_TRY(A->hipMemsetAsync(d_stats, 0, bytes, s));
     if (p->fd.out_w <= 0 || p->fd.out_h <= 0) return MCS_OK;
     const Kernels *kn = nullptr;
-    int rc = kernels(A, p->device, &kn);
+    int rc = kernels(A, p, &kn);
     if (rc) return rc;
     rc = upload_plan_tables(A, p, s);   // (cylinder / lensed plans: their device tables, once)
     if (rc) return rc;
@@ -215,7 +215,7 @@ int gain_apply_frames(const mcs_plan *plan, const uint8_t *d_src, uint8_t *d_dst
     const mcs::Entry A(plan->device);
     if (A.status) return A.status;
     const Kernels *k = nullptr;
-    const int rc = kernels(A, plan->device, &k);
+    const int rc = kernels(A, plan, &k);
     if (rc) return rc;
     return launch_gain(A, k, d_src, d_dst, bytes, src_frame_stride, dst_frame_stride, n_frames, q,
                        d_q, (hipStream_t)stream);
@@ -367,7 +367,7 @@ int mcs_plan_overlap_stats(mcs_plan *p, const uint8_t *const *d_cams,
         s = p->stream;
     }
     const Kernels *k = nullptr;
-    rc = kernels(A, p->device, &k);
+    rc = kernels(A, p, &k);
     if (rc) return rc;
     if (p->ov.step != step_log2) {
         rc = build_overlap(A, p, k, step_log2, s);

@@ -57,7 +57,7 @@ struct KParams {
     int cam_w[MCS_MAX_CAMS], cam_h[MCS_MAX_CAMS];   // sizes of every camera (sorted-label order)
     KStage st[MCS_MAX_STAGES];
     // Lenses (mcs_plan_set_lens, mcs_lens_core.h): one row of kLensDoubles doubles per camera
-    // (fx, fy, cx, cy, 12 coefficients, r2max); bit c of lens_mask: camera c has one, its stage
+    // (fx, fy, cx, cy, 12 coefficients, r2max, model); bit c of lens_mask: camera c has one, its stage
     // map then ends in the raw frame.  A table, not KStage fields: 16 more doubles per stage would
     // push the stream and band-pass kernarg blocks past 4 KB.  Last, so that every other field
     // keeps its kernarg offset.

@@ -446,7 +446,7 @@ int launch_stitch(const Api *A, mcs_plan *p, const mcs::KParams &kp, int n_frame
 {
     if (kp.out_w <= 0 || kp.out_h <= 0 || n_frames <= 0) return MCS_OK;
     const Kernels *k = nullptr;
-    int rc = kernels(A, p->device, &k);
+    int rc = kernels(A, p, &k);
     if (rc) return rc;
     rc = prepare(A, p, s);
     if (rc) return rc;

@@ -265,8 +265,13 @@ bool undistort_map(const double *K, const double *dist, int n_dist, int w, int h
     return true;
 }
 
-int lens_from(const double *K, const double *dist, int n_dist, Lens *L)
+int lens_from(const double *K, const double *dist, int n_dist, Lens *L, int model)
 {
+    if (model != MCS_LENS_PINHOLE && model != MCS_LENS_FISHEYE)
+        return fail(MCS_E_INVALID, "lens model %d (MCS_LENS_PINHOLE or MCS_LENS_FISHEYE)", model);
+    if (model == MCS_LENS_FISHEYE && !(n_dist == 0 || n_dist == 4))
+        return fail(MCS_E_UNSUPPORTED, "fisheye distortion vector of %d coefficients (0 or 4)",
+                    n_dist);
     if (!(n_dist == 0 || n_dist == 4 || n_dist == 5 || n_dist == 8 || n_dist == 12 ||
           n_dist == 14))
         return fail(MCS_E_UNSUPPORTED, "distortion vector of %d coefficients (0, 4, 5, 8, 12 or 14)",
@@ -286,7 +291,8 @@ int lens_from(const double *K, const double *dist, int n_dist, Lens *L)
     L->cx = K[2];
     L->cy = K[5];
     for (int i = 0; i < n_dist && i < 12; i++) L->k[i] = dist[i];
-    L->r2max = lens_r2max(*L);
+    L->model = (double)model;
+    L->r2max = model == MCS_LENS_FISHEYE ? lens_tmax(*L) : lens_r2max(*L);
     return MCS_OK;
 }
 

@@ -138,7 +138,10 @@ struct mcs_plan {
     int32_t *d_map = nullptr;
     // lenses (mcs_plan_set_lens): host rows of the cameras in kp.lens_mask, the device table
     // (MCS_MAX_CAMS rows, allocated once) and whether it lags the host rows
+    // fish_mask: the cameras whose lens is a fisheye one; any: the plan runs the kernels of the
+    // code objects built with the fisheye model (host::kernels)
     mcs::Lens lens[MCS_MAX_CAMS] = {};
+    uint32_t fish_mask = 0;
     double *d_lens = nullptr;
     bool lens_stale = false;
     // exposure gains (mcs_plan_set_gains): q = the gain in 1/256 per camera; enabled by any
@@ -212,6 +215,9 @@ struct Kernels {
 // mcs_prepare.cpp
 // The stitch, sweep and direct multi-band modules' kernels on `device` (looked up once per device).
 int kernels(const Api *A, int device, const Kernels **out);
+// The kernels plan p runs: those of the code objects built with the fisheye model when any of its
+// cameras has a fisheye lens, the ones above otherwise (the same names, the same arguments).
+int kernels(const Api *A, const mcs_plan *p, const Kernels **out);
 // The plan-lifetime device tables (cylinder table, map, lens rows), uploaded when missing / stale.
 int upload_plan_tables(const Api *A, mcs_plan *p, hipStream_t s);
 // Builds p->t unless it stands.  Allocates and synchronises: call before graph capture (the

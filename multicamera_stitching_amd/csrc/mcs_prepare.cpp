@@ -12,17 +12,20 @@
 namespace mcs {
 namespace host {
 
-static Kernels g_k[kMaxDevices];
+static Kernels g_k[kMaxDevices][2];   // [device][fisheye build]
 static std::mutex g_k_mu;
 
-int kernels(const Api *A, int device, const Kernels **out)
+static int kernels_of(const Api *A, int device, bool fish, const Kernels **out)
 {
     if (device < 0 || device >= kMaxDevices) return mcs::fail(MCS_E_INVALID, "device %d", device);
     std::lock_guard<std::mutex> lk(g_k_mu);
-    Kernels &k = g_k[device];
+    Kernels &k = g_k[device][fish ? 1 : 0];
+    const mcs::Module m_stitch = fish ? mcs::kModStitchFish : mcs::kModStitch;
+    const mcs::Module m_sweep = fish ? mcs::kModSweepFish : mcs::kModSweep;
+    const mcs::Module m_direct_mb = fish ? mcs::kModDirectMbFish : mcs::kModDirectMb;
     if (!k.loaded) {
         auto fn = [&](const char *name, hipFunction_t *f) {
-            return mcs::module_function(A, device, mcs::kModStitch, name, f);
+            return mcs::module_function(A, device, m_stitch, name, f);
         };
         char name[64];
         int rc = MCS_OK;
@@ -98,12 +101,12 @@ int kernels(const Api *A, int device, const Kernels **out)
                 for (int jb = 0; jb < 2 && rc == MCS_OK; jb++) {
                     snprintf(name, sizeof(name), "mcs_mb_sweep%s_c%d_j%d", al ? "_a" : "", c,
                              jb ? 4 : 2);
-                    rc = mcs::module_function(A, device, mcs::kModSweep, name,
+                    rc = mcs::module_function(A, device, m_sweep, name,
                                               &k.mb_sweep[c][al][jb]);
                 }
                 snprintf(name, sizeof(name), "mcs_mb_sweep_desc_c%d_i%d", c, al);
                 if (rc == MCS_OK)
-                    rc = mcs::module_function(A, device, mcs::kModSweep, name,
+                    rc = mcs::module_function(A, device, m_sweep, name,
                                               &k.mb_sweep_desc[c][al]);
             }
         if (rc == MCS_OK) rc = fn("mcs_footprint_i0", &k.footprint[0]);
@@ -127,11 +130,11 @@ int kernels(const Api *A, int device, const Kernels **out)
             for (int c = 1; c <= 4 && rc == MCS_OK; c++)
                 for (int i = 0; i < 2 && rc == MCS_OK; i++) {
                     snprintf(name, sizeof(name), "mcs_direct_mb_own_c%d_i%d%s", c, i, g ? "_g" : "");
-                    rc = mcs::module_function(A, device, mcs::kModDirectMb, name,
+                    rc = mcs::module_function(A, device, m_direct_mb, name,
                                               &k.direct_mb_own[g][c][i]);
                     snprintf(name, sizeof(name), "mcs_direct_mb_tile_c%d_i%d%s", c, i, g ? "_g" : "");
                     if (rc == MCS_OK)
-                        rc = mcs::module_function(A, device, mcs::kModDirectMb, name,
+                        rc = mcs::module_function(A, device, m_direct_mb, name,
                                                   &k.direct_mb_tile[g][c][i]);
                 }
         if (rc) return rc;
@@ -139,6 +142,16 @@ int kernels(const Api *A, int device, const Kernels **out)
     }
     *out = &k;
     return MCS_OK;
+}
+
+int kernels(const Api *A, int device, const Kernels **out)
+{
+    return kernels_of(A, device, false, out);
+}
+
+int kernels(const Api *A, const mcs_plan *p, const Kernels **out)
+{
+    return kernels_of(A, p->device, p->fish_mask != 0, out);
 }
 
 // Launch list of the streaming kernel for tiles in launch order: stream_tile deals a list to the
@@ -236,10 +249,13 @@ static int band_lds_tables(const Api *A, mcs_plan *p, std::vector<mcs::MbBand> &
                                      : 0xfffffff0u;
             }
         // descriptors: .x = ring offsets of the tap-a / tap-b windows (4-byte aligned), .y keeps
-        // the weights and takes the window shift sh = tap byte & 3
-        for (int r = 0; r < DR; r++)
+        // the weights and takes the window shift sh = tap byte & 3.  Rows 0 .. R - 1 only: the
+        // descriptor rows past them repeat row R - 1 (read through min(r, R - 1) below), and
+        // rewriting them here too would decode row R - 1's already rewritten value as a frame
+        // offset and index bs[] far outside its rows
+        for (int r = 0; r < R; r++)
             for (int l = 0; l < L; l++) {
-                const uint64_t v = d[std::min(r, R - 1) * L + l];
+                const uint64_t v = d[r * L + l];
                 const uint32_t dx = (uint32_t)v, dy = (uint32_t)(v >> 32);
                 const int64_t oa = dx & 0x7fffffffu, cb = oa % pitch;
                 const int ya = (int)(oa / pitch) - y0, yb = ya + (int)(dx >> 31);
@@ -579,7 +595,7 @@ int upload_plan_tables(const Api *A, mcs_plan *p, hipStream_t s)
 static int build_tables(const Api *A, mcs_plan *p, hipStream_t s)
 {
     const Kernels *k = nullptr;
-    int rc = kernels(A, p->device, &k);
+    int rc = kernels(A, p, &k);
     if (rc) return rc;
     p->gx = (p->fd.out_w + mcs::kTileW - 1) / mcs::kTileW;
     p->gy = (p->fd.out_h + mcs::kTileH - 1) / mcs::kTileH;

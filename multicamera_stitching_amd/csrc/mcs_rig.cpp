@@ -166,12 +166,12 @@ struct mcs_rig_job {
     int64_t *d_stats = nullptr, *h_stats = nullptr;
     // per-camera lenses (mcs_rig_job_set_lens): bit c of lens_mask: camera c has one; lens[c] is
     // its row of the device table (uploaded into the job's buffer before the next capture's chain
-    // when lens_stale), lens_K / lens_dist / lens_nd what the capture's plan is given
+    // when lens_stale), lens_K / lens_dist / lens_nd / lens_model what the capture's plan is given
     uint32_t lens_mask = 0;
     bool lens_stale = false;
     mcs::Lens lens[MCS_MAX_CAMS];
     double lens_K[MCS_MAX_CAMS][9], lens_dist[MCS_MAX_CAMS][14];
-    int lens_nd[MCS_MAX_CAMS];
+    int lens_nd[MCS_MAX_CAMS], lens_model[MCS_MAX_CAMS];
 };
 
 namespace {
@@ -723,7 +723,8 @@ int mcs_rig_job_wait_stitch_batch(mcs_rig_job *j, double *H_io, int *ok_io, int 
         int w = 0, h = 0, c = 0;
         for (int cam = 0; cam < N && r == MCS_OK; cam++)
             if ((j->lens_mask >> cam) & 1u)
-                r = mcs_plan_set_lens(plan, cam, j->lens_K[cam], j->lens_dist[cam], j->lens_nd[cam]);
+                r = mcs_plan_set_lens_model(plan, cam, j->lens_model[cam], j->lens_K[cam],
+                                            j->lens_dist[cam], j->lens_nd[cam]);
         const int blend = j->multiband ? (int)MCS_BLEND_MULTIBAND : j->blend;
         if (r == MCS_OK && blend != MCS_BLEND_NONE) r = mcs_plan_set_blend(plan, blend);
         if (r == MCS_OK) r = mcs_plan_out_shape(plan, &w, &h, &c);
@@ -855,6 +856,12 @@ int mcs_rig_job_set_exposure(mcs_rig_job *j, int step_log2, double alpha, double
 
 int mcs_rig_job_set_lens(mcs_rig_job *j, int cam, const double *K, const double *dist, int n_dist)
 {
+    return mcs_rig_job_set_lens_model(j, cam, MCS_LENS_PINHOLE, K, dist, n_dist);
+}
+
+int mcs_rig_job_set_lens_model(mcs_rig_job *j, int cam, int model, const double *K,
+                               const double *dist, int n_dist)
+{
     mcs::clear_error();
     if (!j) return mcs::fail(MCS_E_INVALID, "NULL job");
     if (cam < 0 || cam >= j->n_cams)
@@ -862,7 +869,7 @@ int mcs_rig_job_set_lens(mcs_rig_job *j, int cam, const double *K, const double 
     mcs::Lens L;
     if (K) {
         if (n_dist < 0 || (n_dist > 0 && !dist)) return mcs::fail(MCS_E_INVALID, "NULL dist");
-        const int rc = mcs::lens_from(K, dist, n_dist, &L);
+        const int rc = mcs::lens_from(K, dist, n_dist, &L, model);
         if (rc) return rc;
     }
     std::lock_guard<std::mutex> lk(j->mu);
@@ -872,6 +879,7 @@ int mcs_rig_job_set_lens(mcs_rig_job *j, int cam, const double *K, const double 
         std::memcpy(j->lens_K[cam], K, sizeof(j->lens_K[cam]));
         for (int i = 0; i < 14; i++) j->lens_dist[cam][i] = i < n_dist ? dist[i] : 0.0;
         j->lens_nd[cam] = n_dist;
+        j->lens_model[cam] = model;
         j->lens_mask |= 1u << cam;
     } else {
         if (!((j->lens_mask >> cam) & 1u)) return MCS_OK;   // none to remove

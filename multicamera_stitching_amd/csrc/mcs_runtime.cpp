@@ -8,6 +8,9 @@ extern "C" const unsigned char mcs_hsaco_stitch_start[];
 extern "C" const unsigned char mcs_hsaco_features_start[];
 extern "C" const unsigned char mcs_hsaco_sweep_start[];
 extern "C" const unsigned char mcs_hsaco_direct_mb_start[];
+extern "C" const unsigned char mcs_hsaco_stitch_fish_start[];
+extern "C" const unsigned char mcs_hsaco_sweep_fish_start[];
+extern "C" const unsigned char mcs_hsaco_direct_mb_fish_start[];
 
 namespace mcs {
 
@@ -18,6 +21,9 @@ std::mutex g_mod_mu;
 const unsigned char *blob(Module m)
 {
     if (m == kModDirectMb) return mcs_hsaco_direct_mb_start;
+    if (m == kModStitchFish) return mcs_hsaco_stitch_fish_start;
+    if (m == kModSweepFish) return mcs_hsaco_sweep_fish_start;
+    if (m == kModDirectMbFish) return mcs_hsaco_direct_mb_fish_start;
     return m == kModStitch ? mcs_hsaco_stitch_start
                            : (m == kModSweep ? mcs_hsaco_sweep_start : mcs_hsaco_features_start);
 }

@@ -316,7 +316,7 @@ int mcs_plan_find_seams(mcs_plan *p, const uint8_t *const *cams, int method, int
     if (rc == MCS_OK) rc = ensure_host_buffers(A, p);
     if (rc == MCS_OK) rc = upload_plan_tables(A, p, p->stream);
     const Kernels *k = nullptr;
-    if (rc == MCS_OK) rc = kernels(A, p->device, &k);
+    if (rc == MCS_OK) rc = kernels(A, p, &k);
     if (rc) return rc;
     const int C = p->fd.channels, n = p->fd.n_cams;
     for (int i = 0; i < n; i++) {

@@ -61,7 +61,7 @@ int direct_launch(mcs_plan *p, mcs::KParams kp, int n_frames, void *stream, Body
     const mcs::Entry A(p->device);
     if (A.status) return A.status;
     const Kernels *k = nullptr;
-    int rc = kernels(A, p->device, &k);
+    int rc = kernels(A, p, &k);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     rc = upload_plan_tables(A, p, s);

@@ -210,7 +210,7 @@ class CaptureEstimator:
         self.pool.shutdown()
 
     def set_lenses(self, lenses):
-        """Per-camera lenses {camera index: (K, dist)}: the estimator is fed RAW frames
+        """Per-camera lenses {camera index: (K, dist) or (K, dist, "fisheye")}: the estimator is fed RAW frames
         (mcs_rig_job_set_lens).  Every slot's rig job, the Python-issued steps (pair_homography /
         estimate_from carry the matched keypoints through lens_unmap_host and drop the ones
         without a valid inverse) and the plans of plan() / stitch() take them; the pair
@@ -222,8 +222,8 @@ class CaptureEstimator:
                 raise KeyError(f"camera {cam} (0..{self.n_cams - 1})")
             if lens is None:
                 continue
-            K, dist = lens
-            table[int(cam)] = _capi._lens_args(K, dist)
+            model = _capi.lens_model(lens[2]) if len(lens) > 2 else _capi.MCS_LENS_PINHOLE
+            table[int(cam)] = _capi._lens_args(lens[0], lens[1]) + (model,)
         for job in self._jobs:
             if job is not None:
                 for cam in range(self.n_cams):
@@ -244,8 +244,8 @@ class CaptureEstimator:
                 self._jobs[slot].set_multiband(True)
             if self.exposure is not None:
                 self._jobs[slot].set_exposure(self.exposure)
-            for cam, (K, dist) in sorted(self.lenses.items()):
-                self._jobs[slot].set_lens(cam, K, dist)
+            for cam, (K, dist, model) in sorted(self.lenses.items()):
+                self._jobs[slot].set_lens(cam, K, dist, model)
         return self._jobs[slot]
 
     def submit(self, frame_ptrs, wait_event: int = 0, slot: int = 0):
@@ -330,8 +330,8 @@ class CaptureEstimator:
         inverse), as the rig job carries them; a camera without a lens keeps its positions."""
         if cam not in self.lenses:
             return xy
-        K, dist = self.lenses[cam]
-        return _capi.lens_unmap_host(K, dist, xy.astype(np.float64)).astype(np.float32)
+        K, dist, model = self.lenses[cam]
+        return _capi.lens_unmap_host(K, dist, xy.astype(np.float64), model).astype(np.float32)
 
     def pair_homography(self, fa, fb, cam_a: int = None, cam_b: int = None):
         """Camera A -> camera B (A = query, as matchKeypoints' ptsA): H or None, matches,
@@ -380,8 +380,8 @@ class CaptureEstimator:
         stages = chain_stages(pair_H, shapes, self.super_mode)
         plan = _capi.Plan([_stage_desc(sb) for sb in stages], self.w, self.h, self.c, self.interp,
                           device=self.device)
-        for cam, (K, dist) in sorted(self.lenses.items()):
-            plan.set_lens(cam, K, dist)
+        for cam, (K, dist, model) in sorted(self.lenses.items()):
+            plan.set_lens(cam, K, dist, model)
         return plan, stages
 
     def stitch(self, frame_ptrs, pair_H, out_ptr: int, out_pitch: int, out_capacity: int,
